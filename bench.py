@@ -17,6 +17,12 @@ final state runs after the timed region (reported as gather_ms).
 
 Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times --steps launches and prints the line (`value`, `ms_per_step` = wall time of
+one timed launch, the status words of the timed launches, `roofline` from the HIP-event kernel time).  --full adds
+what costs work of its own: `cpu_baseline` + `parity` (+ `config1` for the double pendulum), the instruction counts
+and shader clock of `roofline.fp64`, the energy drift over the timed launches, stepHam's divergence figures.
+--dump-outputs DIR writes the final Phase the timed launches returned (DIR/positions.npy, DIR/momenta.npy).
+
 `roofline` has two readings, and says which one binds:
   * the north-star yardstick: `achieved` = 32*n algorithmic bytes per
     trajectory-step -- charged per RK4 step although --rk4-per-step steps are fused per launch and
@@ -24,7 +30,7 @@ Prints ONE JSON line on rank 0.
     with HIP events on the launch stream.  It is NOTIONAL bandwidth: `roofline.hbm_physical` is what
     a launch really moves (state in + state out + status), its GB/s, and the PMC figure it matches
     (`traffic`, static from profiles/, labelled as such);
-  * `roofline.fp64`: what physically bounds the kernel.  fp64 flops and VALU
+  * `roofline.fp64` (--full): what physically bounds the kernel.  fp64 flops and VALU
     instructions per RK4 step are COUNTED from the code object of this system (llvm-objdump of its
     stepping loop, scripts/isa_stats.py), giving achieved TFLOP/s against the 78.6 TFLOP/s vector
     fp64 peak and the fraction of VALU issue slots used (every VALU instruction of a wavefront
@@ -138,9 +144,9 @@ def parse():
                          "(adaptive RKF45, Hamilton.hs:390-402), one stepHam(dt) per launch -- secondary figure")
     ap.add_argument("--calls-per-launch", type=int, default=1,
                     help="--integrator stepham: consecutive stepHam(dt) calls fused into one launch (hamk_step_ham_iterate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline / parity / config1")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work for the all-cores baseline leg")
-    ap.add_argument("--no-isa", action="store_true", help="skip the instruction count of the stepping loop (roofline.fp64)")
+    ap.add_argument("--no-isa", action="store_true", help="--full without the instruction count of the stepping loop (roofline.fp64)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) even with one rank: exercises the multi-GPU code path "
                          "(barrier, max-over-ranks, final all_gather) on a 1-GPU box")
@@ -149,6 +155,14 @@ def parse():
                          "collectives on host copies, ranks may SHARE a GPU (rank r uses cuda:(r mod device count)): the whole "
                          "WORLD_SIZE > 1 path on a 1-GPU box (tests/test_gpu_configs.py)")
     ap.add_argument("--dump-state", default=None, help="rank 0 writes the final state of the WHOLE ensemble (after the gather) to this .npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path returned after its last step -- the final Phase of the whole ensemble -- as "
+                         "DIR/positions.npy and DIR/momenta.npy (float64, [n, trajectories]); above 64 MB in all, a fixed seeded sample "
+                         "of trajectories (the same columns in both files, ascending global index)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: cpu_baseline + parity (+ config1 for the double pendulum), the "
+                         "instruction counts of roofline.fp64 and the shader clock, the energy drift over the timed launches, "
+                         "stepHam's divergence figures.  Off: set up, warm up, time the steps, dump, print the line")
     ap.add_argument("--drift-tol", type=float, default=1e-3,
                     help="per-launch energy check of the timed launches (HAMK_ST_DRIFT); 0 = plain hamk_rk4_steps")
     a = ap.parse_args()
@@ -157,6 +171,23 @@ def parse():
     if a.rk4_per_step is None:
         a.rk4_per_step = DEFAULT_RK4_PER_STEP.get(a.system, 1000)
     return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, q, p):
+    """--dump-outputs: the final Phase (positions, momenta: [n, trajectories] float64) as .npy files.  Above DUMP_LIMIT_BYTES in
+    all, the same fixed seeded sample of trajectories from both arrays, so that two builds' files compare column for column."""
+    n, total = q.shape
+    keep = DUMP_LIMIT_BYTES // (2 * n * 8)
+    if total > keep:
+        idx = np.sort(np.random.default_rng(examples.SEED).choice(total, size=keep, replace=False))
+        sel = torch.from_numpy(idx).to(q.device)
+        q, p = q.index_select(1, sel), p.index_select(1, sel)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in (("positions", q), ("momenta", p)):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(x.cpu().numpy(), dtype=np.float64))
 
 
 def cpu_baseline_leg(spec, s, dt, target_seconds, own_length=None):
@@ -409,18 +440,20 @@ def stepham_bench(a, s, spec, dt, state, dist, dev, rank, world):
     torch.cuda.synchronize()
     el = (time.perf_counter() - t0) / K                      # per stepHam call
     kernel_s = ev0.elapsed_time(ev1) * 1e-3 / max(1, a.steps) / K
-    # divergence: a wavefront runs until its slowest member is done (outside the timed region: one more call, counted)
-    probe = api.stepHam(dt, s, api.Phase(ph.positions.clone(), ph.momenta.clone()))
-    del probe
-    nsub = s.last_nsub.to(torch.float64)
-    per_wave = 64 // lanes
-    Bw = (nsub.numel() // per_wave) * per_wave
-    wmax = nsub[:Bw].reshape(-1, per_wave).amax(1)
+    if rank == 0 and a.dump_outputs:                       # (no gather on this path: rank 0's shard, the whole ensemble at one rank)
+        dump_outputs(a.dump_outputs, ph.positions, ph.momenta)
+    if a.full:
+        # divergence: a wavefront runs until its slowest member is done (outside the timed region: one more call, counted)
+        probe = api.stepHam(dt, s, api.Phase(ph.positions.clone(), ph.momenta.clone()))
+        del probe
+        nsub = s.last_nsub.to(torch.float64)
+        per_wave = 64 // lanes
+        Bw = (nsub.numel() // per_wave) * per_wave
+        wmax = nsub[:Bw].reshape(-1, per_wave).amax(1)
     if rank == 0:
         B = a.batch
         n = spec.n
         calls_per_s = world * B * a.steps / el
-        attempts_per_s = calls_per_s * float(nsub.mean())
         out = {"metric": "stepHam calls/sec (ensemble, adaptive RKF45 GSL semantics)",
                "value": calls_per_s, "unit": "trajectory-stepHam/s", "n_gpus": world,
                "steps": a.steps, "warmup": a.warmup, "ms_per_step": el / a.steps * 1e3,
@@ -428,15 +461,17 @@ def stepham_bench(a, s, spec, dt, state, dist, dev, rank, world):
                "data": "synthetic (per-index splitmix64 initial conditions, seed 20241008)",
                "config": {"workload": f"{a.system} (System {spec.m} {spec.n}) ensemble, stepHam dt={dt}", "trajectories_per_gpu": B,
                           "stepham_calls_per_launch": K,
-                          "kernel_path": ("four lanes per trajectory" if lanes == 4 else "wave-cooperative") if lanes > 1 else "one trajectory per lane", "gsl_api": s.gsl_api},
-               "mean_substeps": float(nsub.mean()), "max_substeps": float(nsub.max()),
-               "rhs_evals_per_s": attempts_per_s * 6,
-               "divergence": {"mean_substeps_per_lane": float(nsub.mean()), "mean_of_wave_max_substeps": float(wmax.mean()),
-                              "lane_utilisation": float(nsub[:Bw].mean() / wmax.mean()),
-                              "note": "a wavefront executes max-over-its-lanes attempts; utilisation = mean / mean-of-wave-max"}}
+                          "kernel_path": ("four lanes per trajectory" if lanes == 4 else "wave-cooperative") if lanes > 1 else "one trajectory per lane", "gsl_api": s.gsl_api}}
+        if a.full:
+            attempts_per_s = calls_per_s * float(nsub.mean())
+            out.update({"mean_substeps": float(nsub.mean()), "max_substeps": float(nsub.max()),
+                        "rhs_evals_per_s": attempts_per_s * 6,
+                        "divergence": {"mean_substeps_per_lane": float(nsub.mean()), "mean_of_wave_max_substeps": float(wmax.mean()),
+                                       "lane_utilisation": float(nsub[:Bw].mean() / wmax.mean()),
+                                       "note": "a wavefront executes max-over-its-lanes attempts; utilisation = mean / mean-of-wave-max"}})
         alg = 32.0 * n * B                                   # a launch reads and writes one Phase per trajectory
         fp64 = {"peak_tflops": FP64_PEAK_TFLOPS, "lanes_per_trajectory": lanes}
-        if not a.no_isa:
+        if a.full and not a.no_isa:
             try:
                 sys.path.insert(0, os.path.join(ROOT, "scripts"))
                 import isa_stats
@@ -454,7 +489,7 @@ def stepham_bench(a, s, spec, dt, state, dist, dev, rank, world):
         out["roofline"] = {"bound": "hbm", "achieved": alg / kernel_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": alg / kernel_s / 1e9 / HBM_PEAK_GBS, "traffic": None, "kernel": "hamk_rkf45_k", "kernel_ms": kernel_s * 1e3,
                            "algorithmic_bytes_per_launch": alg, "physically_binding": "fp64-valu (divergent trip counts)", "fp64": fp64}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             from oracle import oracle
             o = oracle.OracleSystem(spec)
             o.gsl_api = s.gsl_api
@@ -553,7 +588,7 @@ def main():
     q, qd = cfg0.positions, cfg0.velocities
     ph = api.toPhase(s, api.Config(q, qd))               # momenta on device (Hamilton.hs:279-284)
     q, p = ph.positions.clone(), ph.momenta.clone()
-    h0 = api.hamiltonian(s, api.Phase(q, p)).clone()
+    h0 = api.hamiltonian(s, api.Phase(q, p)).clone() if a.full else None
     state = api.Phase(q, p)
 
     def barrier():
@@ -575,8 +610,9 @@ def main():
     status_or.zero_()
     barrier()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    clk = ClockSampler(local_rank)
-    clk.start()
+    clk = ClockSampler(local_rank) if a.full and not a.no_isa else None      # read only by roofline.fp64's issue fraction
+    if clk:
+        clk.start()
     t0 = time.perf_counter()
     ev0.record()                                          # kernels launch on torch's current stream
     for _ in range(a.steps):
@@ -585,7 +621,7 @@ def main():
     ev1.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    sclk_mhz = clk.stop()
+    sclk_mhz = clk.stop() if clk else None
     barrier()
     kernel_s = ev0.elapsed_time(ev1) * 1e-3 / max(1, a.steps)     # avg launch duration, HIP events
     if dist is not None:
@@ -595,12 +631,14 @@ def main():
 
     bad = int(torch.count_nonzero(status_or))
     bad_drift = int(torch.count_nonzero(status_or & 16))
-    h1 = api.hamiltonian(s, state)
-    rel = (h1 - h0).abs() / h0.abs().clamp(min=1.0)
-    drift = float(rel.max())
-    # fixed-step RK4 through a near-singularity (close encounter of the gravitational systems)
-    # shows up as lost energy conservation: counted here, from the hamiltonian before and after
-    drift_flagged = int((rel > 1e-3).sum())
+    drift, drift_flagged = 0.0, 0
+    if a.full:
+        h1 = api.hamiltonian(s, state)
+        rel = (h1 - h0).abs() / h0.abs().clamp(min=1.0)
+        drift = float(rel.max())
+        # fixed-step RK4 through a near-singularity (close encounter of the gravitational systems)
+        # shows up as lost energy conservation: counted here, from the hamiltonian before and after
+        drift_flagged = int((rel > 1e-3).sum())
 
     gather_ms = None
     if dist is not None:                                  # the path's only collective: final gather over xGMI
@@ -620,6 +658,8 @@ def main():
         gq, gp = state.positions, state.momenta
     if rank == 0 and a.dump_state:
         np.savez(a.dump_state, q=gq.cpu().numpy(), p=gp.cpu().numpy())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, gq, gp)
 
     if rank == 0:
         total = a.batch if a.scaling == "strong" else world * a.batch
@@ -643,7 +683,7 @@ def main():
         lanes_per_traj = s.lanes_per_trajectory          # 1, or the cooperative group size the module was built with
         wave = lanes_per_traj >= 16
         fp64 = {"per_gpu_steps_per_s": per_gpu_rate, "peak_tflops": FP64_PEAK_TFLOPS, "lanes_per_trajectory": lanes_per_traj}
-        if not a.no_isa:
+        if a.full and not a.no_isa:
             try:
                 sys.path.insert(0, os.path.join(ROOT, "scripts"))
                 import isa_stats
@@ -694,13 +734,14 @@ def main():
                                           "frac_of_peak": moved / kernel_s / 1e9 / HBM_PEAK_GBS},
                          "fp64": fp64},
             "status_flagged": bad, "status_flagged_drift": bad_drift, "drift_tol_per_launch": DRIFT_TOL,
-            "max_rel_energy_drift": drift, "energy_drift_over_1e-3": drift_flagged,
         }
+        if a.full:
+            out.update({"max_rel_energy_drift": drift, "energy_drift_over_1e-3": drift_flagged})
         if gather_ms is not None:
             out["gather_ms"] = gather_ms
             out["rccl"] = {"world": dist.get_world_size(), "backend": dist.get_backend(),
                            "collectives": "barrier + max-over-ranks timing + ONE all_gather of the final state after the timed region; none on the data path"}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             base, parity = cpu_baseline_leg(spec, s, dt, a.cpu_seconds, a.rk4_per_step)
             base["reference_haskell"] = probe_reference_toolchain()
             out["cpu_baseline"] = base

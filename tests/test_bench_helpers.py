@@ -83,3 +83,25 @@ def test_gpus_flag_starts_one_rank_per_gpu(hamk_lib, monkeypatch):
     with pytest.raises(SystemExit) as e:
         b.main()
     assert "WORLD_SIZE=2" in str(e.value.code)
+
+
+def test_dump_outputs_writes_the_phase_and_samples_past_the_limit(hamk_lib, monkeypatch, tmp_path):
+    """--dump-outputs: positions / momenta as float64 .npy; above the size limit the same seeded columns of both, in
+    ascending order, identical from call to call."""
+    import numpy as np
+    import torch
+    b = _bench()
+    n, total = 2, 1000
+    q = torch.arange(n * total, dtype=torch.float64).reshape(n, total)
+    p = -q
+    b.dump_outputs(str(tmp_path / "all"), q, p)
+    assert np.array_equal(np.load(tmp_path / "all" / "positions.npy"), q.numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "momenta.npy"), p.numpy())
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 2 * n * 8 * 100)    # room for 100 trajectories
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), q, p)
+    sq, sp = np.load(tmp_path / "s1" / "positions.npy"), np.load(tmp_path / "s1" / "momenta.npy")
+    assert sq.shape == sp.shape == (n, 100) and sq.dtype == np.float64
+    cols = sq[0].astype(np.int64)
+    assert np.all(np.diff(cols) > 0) and np.array_equal(sq, q.numpy()[:, cols]) and np.array_equal(sp, -sq)
+    assert np.array_equal(sq, np.load(tmp_path / "s2" / "positions.npy"))
