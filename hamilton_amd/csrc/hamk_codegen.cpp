@@ -671,6 +671,98 @@ void poly_prune(Poly& p, double scale) {
 }
 double poly_abs_sum(const Poly& p) { double s = 0.0; for (const auto& t : p) s += std::fabs(t.second); return s; }
 
+// One sweep of a tape over polynomials: value V[i] and gradient G[i][j] = dV[i]/dq_j of every tape value as polynomials over
+// {q_j, s_k, c_k}, from the polynomials (inV, inG) of the tape's inputs.  slot(operand, V[operand]) names the trig-cache slot whose
+// sincos pair a SIN / COS of that operand reads (-1: none -- not a polynomial).  GS[i][j] is the running magnitude of G[i][j]: the
+// sum of |coefficient| over every contribution BEFORE like terms cancel, the scale poly_prune measures a cancelled term against.
+template <class Slot>
+void poly_sweep(const std::vector<hamk_op>& ops, int n, const std::vector<Poly>& inV, const std::vector<std::vector<Poly>>& inG, Slot slot,
+                std::vector<Poly>& V, std::vector<std::vector<Poly>>& G, std::vector<std::vector<double>>& GS) {
+  const int nops = (int)ops.size();
+  V.assign((size_t)nops, Poly());
+  G.assign((size_t)nops, std::vector<Poly>((size_t)n));
+  GS.assign((size_t)nops, std::vector<double>((size_t)n, 0.0));
+  std::vector<double> VS((size_t)nops, 0.0);
+  for (int i = 0; i < nops; ++i) {
+    const hamk_op& p = ops[(size_t)i];
+    switch (p.op) {
+      case HAMK_OP_CONST: V[i] = poly_const(p.c); VS[i] = std::fabs(p.c); break;
+      case HAMK_OP_INPUT:
+        V[i] = inV[(size_t)p.a]; G[i] = inG[(size_t)p.a]; VS[i] = poly_abs_sum(V[i]);
+        for (int j = 0; j < n; ++j) GS[i][j] = poly_abs_sum(G[i][j]);
+        break;
+      case HAMK_OP_ADD: V[i] = V[p.a]; poly_add(V[i], V[p.b]); for (int j = 0; j < n; ++j) { G[i][j] = G[p.a][j]; poly_add(G[i][j], G[p.b][j]); GS[i][j] = GS[p.a][j] + GS[p.b][j]; } VS[i] = VS[p.a] + VS[p.b]; break;
+      case HAMK_OP_SUB: V[i] = V[p.a]; poly_add(V[i], V[p.b], -1.0); for (int j = 0; j < n; ++j) { G[i][j] = G[p.a][j]; poly_add(G[i][j], G[p.b][j], -1.0); GS[i][j] = GS[p.a][j] + GS[p.b][j]; } VS[i] = VS[p.a] + VS[p.b]; break;
+      case HAMK_OP_NEG: poly_add(V[i], V[p.a], -1.0); for (int j = 0; j < n; ++j) { poly_add(G[i][j], G[p.a][j], -1.0); GS[i][j] = GS[p.a][j]; } VS[i] = VS[p.a]; break;
+      case HAMK_OP_MUL:
+        V[i] = poly_reduce(poly_mul(V[p.a], V[p.b]), n);
+        VS[i] = VS[p.a] * VS[p.b];
+        for (int j = 0; j < n; ++j) {
+          if (!G[p.b][j].empty()) poly_add(G[i][j], poly_mul(V[p.a], G[p.b][j]));
+          if (!G[p.a][j].empty()) poly_add(G[i][j], poly_mul(G[p.a][j], V[p.b]));
+          G[i][j] = poly_reduce(G[i][j], n);
+          GS[i][j] = VS[p.a] * GS[p.b][j] + GS[p.a][j] * VS[p.b];
+        }
+        break;
+      case HAMK_OP_DIV: {
+        if (ops[(size_t)p.b].op != HAMK_OP_CONST || ops[(size_t)p.b].c == 0.0) throw SymFail{};
+        const double r = 1.0 / ops[(size_t)p.b].c;          // (x / c: the numerical path divides; the difference is one rounding of a constant)
+        poly_add(V[i], V[p.a], r); for (int j = 0; j < n; ++j) { poly_add(G[i][j], G[p.a][j], r); GS[i][j] = std::fabs(r) * GS[p.a][j]; }
+        VS[i] = std::fabs(r) * VS[p.a];
+      } break;
+      case HAMK_OP_POWI: {
+        if (p.b < 0 || p.b > 6) throw SymFail{};
+        Poly acc = poly_const(1.0), dacc;                    // x^k and k x^(k-1)
+        for (int e = 0; e < p.b; ++e) { dacc = acc; acc = poly_reduce(poly_mul(acc, V[p.a]), n); }
+        V[i] = acc;
+        VS[i] = std::pow(VS[p.a], (double)p.b);
+        if (p.b >= 1) for (int j = 0; j < n; ++j) if (!G[p.a][j].empty()) {
+          Poly t = poly_mul(dacc, G[p.a][j]); poly_add(G[i][j], t, (double)p.b); G[i][j] = poly_reduce(G[i][j], n);
+          GS[i][j] = (double)p.b * std::pow(VS[p.a], (double)(p.b - 1)) * GS[p.a][j];
+        }
+      } break;
+      case HAMK_OP_SIN: case HAMK_OP_COS: {
+        const int k = slot(p.a, V[p.a]);
+        if (k < 0) throw SymFail{};
+        const int sv = n + 2 * k, cv = sv + 1;
+        const bool is_sin = p.op == HAMK_OP_SIN;
+        V[i] = poly_var(is_sin ? sv : cv);
+        VS[i] = 1.0;
+        for (int j = 0; j < n; ++j)
+          if (!G[p.a][j].empty()) { Poly t = poly_mul(poly_var(is_sin ? cv : sv), G[p.a][j]); poly_add(G[i][j], t, is_sin ? 1.0 : -1.0); G[i][j] = poly_reduce(G[i][j], n); GS[i][j] = GS[p.a][j]; }
+      } break;
+      default: throw SymFail{};                              // sqrt, exp, recip ...: not a polynomial
+    }
+  }
+}
+
+// A polynomial as ONE expression over q[], v[], tc.s[], tc.c[]: the sum of its monomials, each with its own coefficient; only + * ( )
+// and hex-float literals (HIP's default contraction makes the FMAs), no temporaries -- tests parse this text.
+struct PolyNames { int n = 0, vbase = 1 << 30; };            // variable ids: q below n, v from vbase, sincos pairs in between
+static std::string poly_expr(const Poly& p, const PolyNames& nm) {
+  std::ostringstream x;
+  bool first = true;
+  for (const auto& t : p) {
+    std::ostringstream f;
+    bool unit = true;
+    for (const auto& vp : t.first)
+      for (int r = 0; r < vp.second; ++r) {
+        f << (unit ? "" : " * ");
+        unit = false;
+        if (vp.first < nm.n) f << "q[" << vp.first << "]";
+        else if (vp.first >= nm.vbase) f << "v[" << (vp.first - nm.vbase) << "]";
+        else f << "tc." << (((vp.first - nm.n) & 1) ? "c" : "s") << "[" << (vp.first - nm.n) / 2 << "]";
+      }
+    if (!first) x << " + ";
+    first = false;
+    if (unit) x << lit(t.second);
+    else if (t.second == 1.0) x << f.str();
+    else x << lit(t.second) << " * " << f.str();
+  }
+  if (first) x << "0.0";
+  return x.str();
+}
+
 struct SymK {
   bool ok = false;
   int n = 0;
@@ -678,6 +770,8 @@ struct SymK {
   std::vector<Poly> dT;         // dT/dq_i = -1/2 v^T (dK/dq_i) v as a polynomial over {q, s, c, v}; variable ids of v_a: vbase + a
   int vbase = 0;
   bool dt_ok = false;
+  std::vector<Poly> gU;         // dU/dq_i where U . f is a polynomial too (gu_ok)
+  bool gu_ok = false;
   long long sym_ops = 0, num_ops = 0, dt_ops = 0;
 };
 
@@ -690,50 +784,17 @@ SymK symbolic_mass_matrix(const SystemDesc& d, const std::vector<int>& slot_oper
   // (instructions per RK4 step with / without, round 6): chain8 2 720 / 2 708, chain12 6 044 / 6 312, chain16 12 308 / 12 232 -- the compiler's
   // re-associated numerical sum is already the closed form there
   if (n > 7 || d.mapping != HAMK_MAP_LANE) return out;
-  std::vector<int> slot_of(nops, -1);
-  for (size_t k = 0; k < slot_operand.size(); ++k) if (slot_operand[k] >= 0) slot_of[(size_t)slot_operand[k]] = (int)k;
   try {
-    std::vector<Poly> V(nops);
-    std::vector<std::vector<Poly>> G(nops, std::vector<Poly>(n));
-    for (int i = 0; i < nops; ++i) {
-      const hamk_op& p = d.f_ops[i];
-      switch (p.op) {
-        case HAMK_OP_CONST: V[i] = poly_const(p.c); break;
-        case HAMK_OP_INPUT: V[i] = poly_var(p.a); G[i][p.a] = poly_const(1.0); break;
-        case HAMK_OP_ADD: V[i] = V[p.a]; poly_add(V[i], V[p.b]); for (int j = 0; j < n; ++j) { G[i][j] = G[p.a][j]; poly_add(G[i][j], G[p.b][j]); } break;
-        case HAMK_OP_SUB: V[i] = V[p.a]; poly_add(V[i], V[p.b], -1.0); for (int j = 0; j < n; ++j) { G[i][j] = G[p.a][j]; poly_add(G[i][j], G[p.b][j], -1.0); } break;
-        case HAMK_OP_NEG: poly_add(V[i], V[p.a], -1.0); for (int j = 0; j < n; ++j) poly_add(G[i][j], G[p.a][j], -1.0); break;
-        case HAMK_OP_MUL:
-          V[i] = poly_reduce(poly_mul(V[p.a], V[p.b]), n);
-          for (int j = 0; j < n; ++j) {
-            if (!G[p.b][j].empty()) poly_add(G[i][j], poly_mul(V[p.a], G[p.b][j]));
-            if (!G[p.a][j].empty()) poly_add(G[i][j], poly_mul(G[p.a][j], V[p.b]));
-            G[i][j] = poly_reduce(G[i][j], n);
-          }
-          break;
-        case HAMK_OP_DIV: {
-          if (d.f_ops[p.b].op != HAMK_OP_CONST || d.f_ops[p.b].c == 0.0) throw SymFail{};
-          const double r = 1.0 / d.f_ops[p.b].c;            // (x / c: the numerical path divides; the difference is one rounding of a constant)
-          poly_add(V[i], V[p.a], r); for (int j = 0; j < n; ++j) poly_add(G[i][j], G[p.a][j], r);
-        } break;
-        case HAMK_OP_POWI: {
-          if (p.b < 0 || p.b > 6) throw SymFail{};
-          Poly acc = poly_const(1.0), dacc;                  // x^k and k x^(k-1)
-          for (int e = 0; e < p.b; ++e) { dacc = acc; acc = poly_reduce(poly_mul(acc, V[p.a]), n); }
-          V[i] = acc;
-          if (p.b >= 1) for (int j = 0; j < n; ++j) if (!G[p.a][j].empty()) { Poly t = poly_mul(dacc, G[p.a][j]); poly_add(G[i][j], t, (double)p.b); G[i][j] = poly_reduce(G[i][j], n); }
-        } break;
-        case HAMK_OP_SIN: case HAMK_OP_COS: {
-          const int k = slot_of[p.a];
-          if (k < 0) throw SymFail{};
-          const int sv = n + 2 * k, cv = sv + 1;
-          const bool is_sin = p.op == HAMK_OP_SIN;
-          V[i] = poly_var(is_sin ? sv : cv);
-          for (int j = 0; j < n; ++j)
-            if (!G[p.a][j].empty()) { Poly t = poly_mul(poly_var(is_sin ? cv : sv), G[p.a][j]); poly_add(G[i][j], t, is_sin ? 1.0 : -1.0); G[i][j] = poly_reduce(G[i][j], n); }
-        } break;
-        default: throw SymFail{};                            // sqrt, exp, recip ...: not a polynomial
-      }
+    std::vector<Poly> V;
+    std::vector<std::vector<Poly>> G;
+    std::vector<std::vector<double>> GS;
+    {
+      std::vector<Poly> inV((size_t)n);
+      std::vector<std::vector<Poly>> inG((size_t)n, std::vector<Poly>((size_t)n));
+      for (int j = 0; j < n; ++j) { inV[(size_t)j] = poly_var(j); inG[(size_t)j][(size_t)j] = poly_const(1.0); }
+      std::vector<int> slot_of(nops, -1);
+      for (size_t k = 0; k < slot_operand.size(); ++k) if (slot_operand[k] >= 0) slot_of[(size_t)slot_operand[k]] = (int)k;
+      poly_sweep(d.f_ops, n, inV, inG, [&](int operand, const Poly&) { return slot_of[(size_t)operand]; }, V, G, GS);
     }
     out.k.resize((size_t)n * (n + 1) / 2);
     size_t e = 0;
@@ -813,69 +874,71 @@ SymK symbolic_mass_matrix(const SystemDesc& d, const std::vector<int>& slot_oper
       // n (n - 1) terms of degree four -- counted from the code objects, chain4 -3 % and chain6 +7 % instructions per step against the
       // directional second sweep, whose structural zeros the compiler already strips: the chains keep that sweep (and the symbolic K)
       out.dt_ok = fits && out.dt_ops <= 12LL * n;
+      // grad U where U . f is a polynomial as well (U = g sum m_k y_k of every pendulum: dU/dq_i = c_i sin q_i): the potential's tape
+      // swept over the polynomials of f's outputs (U cartesian) or over q.  Its SIN / COS sites read the pair of the slot of f whose
+      // operand is the same polynomial; one without such a slot, or any other function (twoBody's 1 / r, spring's exponentials,
+      // threeBodyPolar's square roots): no symbolic gradient, the Jet1 sweep stays.  Cancelled terms are pruned as K's are, against the
+      // running magnitude of the gradient.  Only where dT/dq is symbolic too: a system that keeps the second-order sweep (the chains
+      // n <= 7, whose U is the pendulums' polynomial) needs the Jet1 sweep of f for it anyway, its gradient of U rides on that sweep for
+      // n more operations, and ham_eqs has no branch that mixes the two -- not built, not measured.
+      if (out.dt_ok) {
+        try {
+          const bool cart = d.u_space == HAMK_U_CARTESIAN;
+          const int nin = cart ? m : n;
+          std::vector<Poly> inV((size_t)nin);
+          std::vector<std::vector<Poly>> inG((size_t)nin, std::vector<Poly>((size_t)n));
+          for (int k = 0; k < nin; ++k) {
+            if (cart) { inV[(size_t)k] = V[(size_t)d.f_outs[k]]; inG[(size_t)k] = G[(size_t)d.f_outs[k]]; }
+            else { inV[(size_t)k] = poly_var(k); inG[(size_t)k][(size_t)k] = poly_const(1.0); }
+          }
+          std::vector<Poly> UV;
+          std::vector<std::vector<Poly>> UG;
+          std::vector<std::vector<double>> US;
+          poly_sweep(d.u_ops, n, inV, inG, [&](int, const Poly& arg) {
+            for (int k = 0; k < nslots; ++k) if (slot_operand[(size_t)k] >= 0 && V[(size_t)slot_operand[(size_t)k]] == arg) return k;
+            return -1;
+          }, UV, UG, US);
+          out.gU.assign((size_t)n, Poly());
+          bool short_enough = true;
+          for (int i = 0; i < n; ++i) {
+            Poly g = poly_reduce(UG[(size_t)d.u_out][(size_t)i], n);
+            poly_prune(g, US[(size_t)d.u_out][(size_t)i]);
+            if (g.size() > 64) short_enough = false;
+            out.gU[(size_t)i] = g;
+          }
+          out.gu_ok = short_enough;
+        } catch (const SymFail&) { out.gu_ok = false; }
+      }
     }
   } catch (const SymFail&) { out.ok = false; out.dt_ok = false; }
   return out;
 }
 
-static std::string sym_poly_expr(const Poly& p, int n, int vbase) {
-  std::ostringstream x;
-  bool first = true;
-  for (const auto& t : p) {
-    std::ostringstream f;
-    bool unit = true;
-    for (const auto& vp : t.first)
-      for (int r = 0; r < vp.second; ++r) {
-        f << (unit ? "" : " * ");
-        unit = false;
-        if (vp.first < n) f << "q[" << vp.first << "]";
-        else if (vp.first >= vbase) f << "v[" << (vp.first - vbase) << "]";
-        else f << "tc." << (((vp.first - n) & 1) ? "c" : "s") << "[" << (vp.first - n) / 2 << "]";
-      }
-    if (!first) x << " + ";
-    first = false;
-    if (unit) x << lit(t.second);
-    else if (t.second == 1.0) x << f.str();
-    else x << lit(t.second) << " * " << f.str();
-  }
-  if (first) x << "0.0";
-  return x.str();
-}
-
 void emit_symbolic_dt(std::ostringstream& o, const SymK& sk) {
+  PolyNames nm; nm.n = sk.n; nm.vbase = sk.vbase;
   o << "  // dT/dq = -1/2 v^T (dK/dq) v from the symbolic K (" << sk.dt_ops << " operations): no second-order sweep of f\n";
   o << "  template <class TC> __device__ __forceinline__ static void dT_sym(const double (&q)[N], const double (&v)[N], const TC& tc, double (&dT)[N]) {\n";
-  for (int i = 0; i < sk.n; ++i) o << "    dT[" << i << "] = " << sym_poly_expr(sk.dT[(size_t)i], sk.n, sk.vbase) << ";\n";
+  for (int i = 0; i < sk.n; ++i) o << "    dT[" << i << "] = " << poly_expr(sk.dT[(size_t)i], nm) << ";\n";
+  o << "  }\n";
+}
+
+void emit_symbolic_gu(std::ostringstream& o, const SymK& sk) {
+  PolyNames nm; nm.n = sk.n;
+  o << "  // grad U of the polynomial U . f: no first-order sweep of f and U\n";
+  o << "  template <class TC> __device__ __forceinline__ static void gU_sym(const double (&q)[N], const TC& tc, double (&gU)[N]) {\n";
+  for (int i = 0; i < sk.n; ++i) o << "    gU[" << i << "] = " << poly_expr(sk.gU[(size_t)i], nm) << ";\n";
   o << "  }\n";
 }
 
 void emit_symbolic_k(std::ostringstream& o, const SymK& sk) {
   const int n = sk.n;
+  PolyNames nm; nm.n = n;
   o << "  // K = J^T M J derived symbolically (sin^2 + cos^2 = 1 applied; " << sk.sym_ops << " operations against " << sk.num_ops << " for the numerical sum)\n";
   o << "  template <class TC> __device__ __forceinline__ static void mass_matrix_sym(const double (&q)[N], const TC& tc, double (&K)[N][N]) {\n";
   size_t e = 0;
   for (int a = 0; a < n; ++a)
     for (int b = a; b < n; ++b, ++e) {
-      std::ostringstream x;
-      bool first = true;
-      for (const auto& t : sk.k[e]) {
-        std::ostringstream f;
-        bool unit = true;
-        for (const auto& vp : t.first)
-          for (int r = 0; r < vp.second; ++r) {
-            f << (unit ? "" : " * ");
-            unit = false;
-            if (vp.first < n) f << "q[" << vp.first << "]";
-            else f << "tc." << (((vp.first - n) & 1) ? "c" : "s") << "[" << (vp.first - n) / 2 << "]";
-          }
-        if (!first) x << " + ";
-        first = false;
-        if (unit) x << lit(t.second);
-        else if (t.second == 1.0) x << f.str();
-        else x << lit(t.second) << " * " << f.str();
-      }
-      if (first) x << "0.0";
-      o << "    K[" << a << "][" << b << "] = " << x.str() << ";\n";
+      o << "    K[" << a << "][" << b << "] = " << poly_expr(sk.k[e], nm) << ";\n";
       if (a != b) o << "    K[" << b << "][" << a << "] = K[" << a << "][" << b << "];\n";
     }
   o << "  }\n";
@@ -1043,6 +1106,10 @@ std::string generate_source(const SystemDesc& d) {
     o << "  static constexpr bool HAS_SYM_DT = " << ((sk.ok && sk.dt_ok) ? "true" : "false") << ";\n";
     if (sk.ok && sk.dt_ok) emit_symbolic_dt(o, sk);
     else o << "  template <class TC> __device__ __forceinline__ static void dT_sym(const double (&)[N], const double (&)[N], const TC&, double (&)[N]) {}\n";
+    const bool gu = sk.ok && sk.dt_ok && sk.gu_ok;
+    o << "  static constexpr bool HAS_SYM_GU = " << (gu ? "true" : "false") << ";\n";
+    if (gu) emit_symbolic_gu(o, sk);
+    else o << "  template <class TC> __device__ __forceinline__ static void gU_sym(const double (&)[N], const TC&, double (&)[N]) {}\n";
   }
   o << "  static constexpr int NTRIG_F = " << ntrig_f << ";\n";
   o << "  static constexpr int NTRIG_U = " << ntrig_u << ";\n";

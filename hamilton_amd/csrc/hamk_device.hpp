@@ -1143,8 +1143,17 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
   constexpr bool BURST = (HAMK_TRIG_BURST == 2 || (HAMK_TRIG_BURST == 1 && BURST_OK)) && TRIG_IN == TRIG_LUT && S::TRIG_ALL_INPUTS && S::NTRIG_F >= 2;
   if constexpr (BURST) trig_burst_lut<S>(q, tc);
   constexpr int TRIG = BURST ? TRIG_REUSE : TRIG_IN;
-  double K[N][N], gU[N], U, v[N], dT[N];
-  if constexpr (S::HAS_SYM_K && S::HAS_SYM_DT) {
+  double K[N][N], gU[N], v[N], dT[N];
+  if constexpr (S::HAS_SYM_K && S::HAS_SYM_DT && S::HAS_SYM_GU) {
+    // K, dT/dq = -1/2 v^T (dK/dq) v and grad U all from the generator's polynomials (hamk_codegen.cpp symbolic_mass_matrix): f is
+    // evaluated in plain doubles, only to fill the sincos pairs
+    double x[M];
+    S::template coords<double, TRIG>(q, x, tc);
+    S::mass_matrix_sym(q, tc, K);
+    solve_spd<N, S::INERTIA_POS>(K, p, v, st);
+    S::gU_sym(q, tc, gU);
+    S::dT_sym(q, v, tc, dT);
+  } else if constexpr (S::HAS_SYM_K && S::HAS_SYM_DT) {
     // K and dT/dq = -1/2 v^T (dK/dq) v from the generator's symbolic mass matrix (hamk_codegen.cpp symbolic_mass_matrix): the
     // first-order sweep remains for dU/dq (and fills the sincos pairs); its Jacobian is dead code where U is over q
     Jet1<N> qj[N], xj[M];
@@ -1152,6 +1161,7 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
     S::template coords<Jet1<N>, TRIG>(qj, xj, tc);
     S::mass_matrix_sym(q, tc, K);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
+    double U;
     grad_potential<S>(qj, xj, gU, U, tc);
     S::dT_sym(q, v, tc, dT);
   } else if constexpr (MODE_H) {
@@ -1172,6 +1182,7 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
     }
     if constexpr (S::HAS_SYM_K) S::mass_matrix_sym(q, tc, K); else mass_matrix<S>(xj, K);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
+    double U;
     grad_potential<S>(qj, xj, gU, U, tc);
 #pragma unroll
     for (int i = 0; i < N; ++i) dT[i] = 0.0;
@@ -1195,6 +1206,7 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
     S::template coords<Jet1<N>, TRIG>(qj, xj, tc);
     if constexpr (S::HAS_SYM_K) S::mass_matrix_sym(q, tc, K); else mass_matrix<S>(xj, K);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
+    double U;
     grad_potential<S>(qj, xj, gU, U, tc);
     if constexpr (S::MODE_R) {
       // MODE_R: the contraction is a gradient -- one forward (value, tangent along qd) pass and one
