@@ -38,10 +38,19 @@ def jobs():
     for n in ("opcodeZoo", "doublePendulum", "spring", "threeBodyPolar"):
         for mode in "HDR":
             for loop in (None, "1"):
-                env = {"HAMK_AD_MODE": mode}
+                env = {"HAMK_AD_MODE": mode, "HAMK_K_SYMBOLIC": "0"}      # tests/test_gpu_parity.py test_all_codegen_variants_agree: the jets, not the symbolic right-hand side
                 if loop:
                     env["HAMK_RK4_LOOP"] = loop
                 out.append((n, env, False))
+        out.append((n, {"HAMK_RK4_LOOP": "1"}, False))                    # ... and the default build as one more variant
+    # the symbolic right-hand side and the jets it replaces, side by side (tests/test_gpu_symbolic_rhs.py): the family of
+    # tests/symbolic_family.py and the headline systems with HAMK_K_SYMBOLIC=0 (their default builds are the plain jobs above)
+    import symbolic_family
+    for seed in symbolic_family.SEEDS:
+        out.append((f"symfam{seed}", {}, False))
+        out.append((f"symfam{seed}", {"HAMK_K_SYMBOLIC": "0"}, False))
+    for n in ("doublePendulum", "twoBody", "spring", "threeBodyPolar"):
+        out.append((n, {"HAMK_K_SYMBOLIC": "0"}, False))
     for n in ("doublePendulum", "twoBody", "spring", "threeBodyPolar", "pendulum", "chain8", "chain16"):
         out.append((n, {"HAMK_TRIG_LUT": "0"}, False))
         out.append((n, {"HAMK_TRIG_LUT": "1"}, False))
@@ -94,6 +103,9 @@ def build(job):
         elif name.startswith("polytrig"):
             from test_gpu_random_systems import poly_trig_spec
             spec = poly_trig_spec(int(name[8:]))
+        elif name.startswith("symfam"):
+            import symbolic_family
+            spec = symbolic_family.spec(int(name[6:]))
         else:
             spec = examples.get(name)
         s = api.system_from_spec(spec)

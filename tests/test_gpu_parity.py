@@ -41,9 +41,9 @@ def relerr(a, b):
 
 
 # ---------------------------------------------------------------- T1: golden fixtures
-def check_golden_points(api, s, name):
-    g = load_golden(name)
-    pts = g["points"]
+def check_golden_points(api, s, name, pts=None):
+    """`pts`: the points of one block of a fixture file that holds several systems (symbolic_family.json)."""
+    pts = load_golden(name)["points"] if pts is None else pts
     q = np.stack([fvec(p["q"]) for p in pts], axis=1)
     qd = np.stack([fvec(p["qd"]) for p in pts], axis=1)
     p = np.stack([fvec(pt["p"]) for pt in pts], axis=1)
@@ -605,21 +605,32 @@ def test_all_codegen_variants_agree(api, oracle_lib, name, monkeypatch):
     odq, odp, _ = o.hameqs_batch(q, p)
     oq, op = o.rk4_steps_batch(q, p, spec.dt, 3)
     sq, sp, sns = o.step_ham_batch(q, p, 0.01)
-    for mode in ("H", "D", "R"):
+    # the symbolic right-hand side (hamk_codegen.cpp symbolic_mass_matrix) is taken BEFORE MODE_H / MODE_R are looked at: the matrix runs
+    # with HAMK_K_SYMBOLIC=0, so that the jets the mode names are what computes; the default build is one more variant
+    for mode in ("H", "D", "R", "default"):
         # RK4 body: the library's own choice (unrolled for small kernels, stage loop above the
         # 64 KiB code-size guard -- e.g. opcodeZoo) and the stage loop forced.  The unrolled body is
         # deliberately NOT forced on kernels the guard would reject: hipcc/ROCm 7.2 miscompiles the
         # 98 KiB unrolled opcodeZoo kernel (1e-4 off after one step on every lane, status clean).
         for loop in (None, "1"):
-            monkeypatch.setenv("HAMK_AD_MODE", mode)
+            if mode == "default":
+                monkeypatch.delenv("HAMK_AD_MODE", raising=False)
+                monkeypatch.delenv("HAMK_K_SYMBOLIC", raising=False)
+            else:
+                monkeypatch.setenv("HAMK_AD_MODE", mode)
+                monkeypatch.setenv("HAMK_K_SYMBOLIC", "0")
             if loop is None:
                 monkeypatch.delenv("HAMK_RK4_LOOP", raising=False)
             else:
                 monkeypatch.setenv("HAMK_RK4_LOOP", loop)
             s = api.system_from_spec(spec)
             assert s.kernel_bytes("hamk_rk4_steps_k") < 96 * 1024
-            assert f"MODE_H = {'true' if mode == 'H' else 'false'}" in s.source
-            assert f"MODE_R = {'true' if mode == 'R' else 'false'}" in s.source
+            if mode == "default":
+                assert ("HAS_SYM_K = true" in s.source) == (name != "opcodeZoo") and ("HAS_SYM_DT = true" in s.source) == (name != "opcodeZoo")
+            else:
+                assert f"MODE_H = {'true' if mode == 'H' else 'false'}" in s.source
+                assert f"MODE_R = {'true' if mode == 'R' else 'false'}" in s.source
+                assert "HAS_SYM_K = false" in s.source and "HAS_SYM_DT = false" in s.source and "HAS_SYM_GU = false" in s.source
             dq, dp = api.hamEqs(s, api.Phase(q, p))
             assert relerr(dq, odq) < 1e-11 and relerr(dp, odp) < 1e-11, (name, mode, loop, relerr(dp, odp))
             ph = api.rk4Steps(spec.dt, 3, s, api.Phase(q, p))

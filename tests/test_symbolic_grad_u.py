@@ -8,37 +8,18 @@ import numpy as np
 import pytest
 
 from hamilton_amd import examples as E
+from symbolic_text import HEX, as_python, emitted, trig_input_table
 
 SYMBOLIC = ["pendulum", "doublePendulum", "doublePendulumReadme", "room", "twoBody", "spring", "threeBodyPolar", "chain4", "chain6"]
 # polynomial U AND symbolic dT/dq.  room, spring: exponentials; twoBody: 1 / r; threeBodyPolar: square roots; chain4, chain6: the
 # pendulums' polynomial U, but their dT/dq keeps the second-order sweep and grad U rides on its first-order part (the generator's rule)
 WITH_GRAD_U = ["pendulum", "doublePendulum", "doublePendulumReadme"]
-HEX = r"-?0x[0-9a-f.]+p[+-]\d+"
 
 
 @pytest.fixture(scope="module")
 def api(hamk_lib):
     from hamilton_amd import api as _api
     return _api
-
-
-def emitted(src, fn):
-    """{target: C++ expression} of one generated function, None where the module has an empty stub."""
-    m = re.search(r"static void %s\(const double \(&q\)\[N\].*?\{\n(.*?)\n  \}" % fn, src, re.S)
-    if not m:
-        return None
-    return {t: e for t, e in re.findall(r"^\s*(\w+(?:\[\d+\])+) = ([^;]*);", m.group(1), re.M)}
-
-
-def as_python(e):
-    """The substitution tests/test_symbolic_k.py applies (one parenthesis on either side of a hex literal goes with it)."""
-    e = re.sub(r"\(?(" + HEX + r")\)?", lambda m: repr(float.fromhex(m.group(1))), e)
-    return e.replace("tc.s[", "s[").replace("tc.c[", "c[")
-
-
-def trig_slots(src):
-    m = re.search(r"trig_input\(int slot\) \{\n\s*constexpr int w\[\d+\] = \{([^}]*)\}", src)
-    return [int(t) for t in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", SYMBOLIC)
@@ -53,7 +34,7 @@ def test_symbolic_grad_u_against_the_oracle(api, oracle_lib, name):
         return
     assert sorted(g) == ["gU[%d]" % i for i in range(spec.n)]
     o = oracle_lib.OracleSystem(spec)
-    slots = trig_slots(src)
+    slots = trig_input_table(src)
     qs, _ = E.sample_config(spec, 31, 64)
     for k in range(qs.shape[1]):
         q = [float(x) for x in qs[:, k]]

@@ -3,37 +3,11 @@ inputs and in sincos of polynomial arguments, K = J^T M J (Hamilton.hs:380) is d
 dT/dq = -1/2 v^T (dK/dq) v (Hamilton.hs:382-385) follows from it -- no second-order sweep.  CPU checks: which systems get it, what it looks
 like for the reference's examples, and its VALUES: the emitted expressions are evaluated here (numpy) against the oracle's J^T M J and
 against central differences of themselves.  The kernels that use it are compared with the oracle in the host emulation and on the GPU."""
-import re
-
 import numpy as np
 import pytest
 
 from hamilton_amd import examples as E
-
-
-def sym_functions(src):
-    """{"K": {(a, b): python expression}, "dT": {i: expression}} parsed from a generated module (None where the module has none)."""
-    def body(name):
-        m = re.search(r"static void %s\(const double \(&q\)\[N\].*?\{\n(.*?)\n  \}" % name, src, re.S)
-        return m.group(1) if m else None
-    hexf = lambda e: re.sub(r"\(?(-?0x[0-9a-f.]+p[+-]\d+)\)?", lambda m: repr(float.fromhex(m.group(1))), e)
-    fix = lambda e: hexf(e).replace("tc.s[", "s[").replace("tc.c[", "c[")
-    out = {"K": None, "dT": None}
-    kb, db = body("mass_matrix_sym"), body("dT_sym")
-    if kb:
-        out["K"] = {}
-        for a, b, e in re.findall(r"K\[(\d+)\]\[(\d+)\] = ([^;]*);", kb):
-            if not e.startswith("K["):
-                out["K"][(int(a), int(b))] = fix(e)
-    if db:
-        out["dT"] = {int(i): fix(e) for i, e in re.findall(r"dT\[(\d+)\] = ([^;]*);", db)}
-    return out
-
-
-def trig_slots(src, spec):
-    """operand of every trig-cache slot as a function of q: the slots of these systems are sincos of INPUTS (trig_input table)."""
-    m = re.search(r"trig_input\(int slot\) \{\n\s*constexpr int w\[\d+\] = \{([^}]*)\}", src)
-    return [int(t) for t in m.group(1).split(",")]
+from symbolic_text import sym_functions, trig_input_table
 
 
 @pytest.fixture(scope="module")
@@ -70,7 +44,7 @@ def test_symbolic_values_against_the_oracle(api, oracle_lib, name):
     src = api.system_from_spec(spec).source
     f = sym_functions(src)
     assert f["K"] is not None
-    slots = trig_slots(src, spec)
+    slots = trig_input_table(src)
     o = oracle_lib.OracleSystem(spec)
     qs, qds = E.sample_config(spec, 17, 12)
     n = spec.n
