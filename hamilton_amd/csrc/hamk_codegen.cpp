@@ -132,14 +132,20 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
       fused_rsqrt[i] = 1;
       done[ops[i].a] = 2;                                   // the square root itself is never emitted
     }
-  // exp(a x + b2) = exp(a x + b1) * exp(b2 - b1): two exponentials whose arguments are the SAME affine function of the same tape value
-  // up to a constant offset -- the two walls of a rail (Examples.hs:155-156: logistic(-1.5, ...) r and logistic(1.5, ...) r), the four walls
-  // of a room -- share one evaluation; the second is the first times a constant (its jet follows by scaling: the chain rule is exact).
-  // ~35 instructions per evaluation saved; the product carries the first exponential's rounding plus the constant's (2 ulp), and
-  // overflows / underflows where the direct evaluation would be within e^+-700 of doing so (offsets beyond 600 are left alone).
+  // exp(a x + b2) = exp(a x + b1) * exp(b2 - b1): exponentials whose arguments are the SAME affine function of the same tape value up to a
+  // constant offset -- the two walls of a rail (Examples.hs:155-156: logistic(-1.5, ...) r and logistic(1.5, ...) r), the four walls of a
+  // room -- share one evaluation: the member with the LARGEST offset is evaluated as written (hoisted, with the affine chain of its
+  // argument, to where the first member stands), every other member within 600 below it is that value times a constant e^delta,
+  // 2.7e-261 <= e^delta <= 1 (its jet follows by scaling: the chain rule is exact).  ~35 instructions per evaluation saved.  Range: the
+  // evaluated member is bit for bit what the tape says; a derived member is never larger than it, so wherever the tape as written is
+  // finite the product is finite, and it carries the evaluated member's rounding plus the constant's and the product's (2 ulp) as long
+  // as the evaluated member is a normal number -- when that one is subnormal or zero, the derived member's true value is below
+  // 2.3e-308 too and the product is within 5e-324 of it.  (Until this rule the FIRST member in tape order was the one evaluated: a
+  // subnormal first member gave a derived member of order one a handful of correct bits, an overflowed one gave inf.)  Members further
+  // than 600 below the evaluated one start a group of their own; a derived member is never the one another is derived from.
   struct Affine { int base; double slope, off; };
   std::vector<Affine> aff((size_t)nops);
-  std::vector<int> exp_of(nops, -1);                       // exp node -> the earlier exp node it is a constant multiple of
+  std::vector<int> exp_of(nops, -1);                       // exp node -> the exp node (earlier or later on the tape) it is a constant multiple of
   std::vector<double> exp_factor(nops, 1.0);
   {
     auto isc = [&](int i) { return ops[i].op == HAMK_OP_CONST; };
@@ -157,15 +163,23 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
       if (p.op == HAMK_OP_CONST) a = {-1, 0.0, p.c};
       aff[(size_t)i] = a;
     }
+    std::vector<char> settled(nops, 0);                    // evaluated as written, or derived
+    auto same_line = [&](int i, int j) {
+      const Affine& ai = aff[(size_t)ops[i].a]; const Affine& aj = aff[(size_t)ops[j].a];
+      return aj.base == ai.base && aj.slope == ai.slope;
+    };
     for (int i = 0; i < nops; ++i) {
-      if (ops[i].op != HAMK_OP_EXP) continue;
-      const Affine& ai = aff[(size_t)ops[i].a];
-      if (ai.base < 0) continue;
-      for (int j = 0; j < i; ++j) {
-        if (ops[j].op != HAMK_OP_EXP || exp_of[j] >= 0) continue;
-        const Affine& aj = aff[(size_t)ops[j].a];
-        const double delta = ai.off - aj.off;
-        if (aj.base == ai.base && aj.slope == ai.slope && std::fabs(delta) <= 600.0) { exp_of[i] = j; exp_factor[i] = std::exp(delta); break; }
+      if (ops[i].op != HAMK_OP_EXP || aff[(size_t)ops[i].a].base < 0) continue;
+      while (!settled[i]) {
+        int top = i;                                       // the largest offset among the members still open (ties: the first on the tape)
+        for (int j = i + 1; j < nops; ++j)
+          if (ops[j].op == HAMK_OP_EXP && !settled[j] && same_line(i, j) && aff[(size_t)ops[j].a].off > aff[(size_t)ops[top].a].off) top = j;
+        settled[top] = 1;
+        for (int j = i; j < nops; ++j) {
+          if (ops[j].op != HAMK_OP_EXP || settled[j] || !same_line(i, j)) continue;
+          const double delta = aff[(size_t)ops[j].a].off - aff[(size_t)ops[top].a].off;      // <= 0
+          if (delta >= -600.0) { exp_of[j] = top; exp_factor[j] = std::exp(delta); settled[j] = 1; }
+        }
       }
     }
   }
@@ -210,10 +224,20 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
     }
     return std::string(pfx) + std::to_string(i);
   };
-  for (int i = 0; i < nops; ++i) {
-    if (done[i]) continue;
+  std::function<void(int)> emit_one = [&](int i) {
+    if (done[i]) return;
     const hamk_op& p = ops[i];
-    if (inline_scale[i]) { done[i] = 2; continue; }
+    if (inline_scale[i]) { done[i] = 2; return; }
+    if (p.op == HAMK_OP_EXP && exp_of[i] > i && !done[exp_of[i]]) {
+      // the member this one is derived from stands later on the tape: it and what its argument still needs (affine operations on a
+      // value that is already defined, and constants) are emitted here
+      std::function<void(int)> ensure = [&](int k) {
+        if (done[k] || ops[k].op == HAMK_OP_INPUT) return;
+        if (ops[k].op != HAMK_OP_CONST) { ensure(ops[k].a); if (is_binary(ops[k].op)) ensure(ops[k].b); }
+        emit_one(k);
+      };
+      ensure(exp_of[i]);
+    }
     o << "    ";
     switch (p.op) {
       case HAMK_OP_CONST: o << "const double " << v(i) << " = " << lit(p.c) << ";\n"; break;
@@ -260,7 +284,8 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
           done[j] = 2;
         }
     }
-  }
+  };
+  for (int i = 0; i < nops; ++i) emit_one(i);
   if (slot_operand) {
     slot_operand->assign(nslots, -1);
     for (int i = 0; i < nops; ++i)

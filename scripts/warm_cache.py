@@ -51,6 +51,12 @@ def jobs():
         out.append((f"symfam{seed}", {"HAMK_K_SYMBOLIC": "0"}, False))
     for n in ("doublePendulum", "twoBody", "spring", "threeBodyPolar"):
         out.append((n, {"HAMK_K_SYMBOLIC": "0"}, False))
+    # the generator's per-node rewrites (tests/test_gpu_codegen_rewrites.py): the family of tests/rewrite_family.py on the default build,
+    # the reverse sweep and the two cooperative mappings, forced through the ABI's options as the tests force them
+    import rewrite_family
+    for key in rewrite_family.KEYS:
+        for variant in rewrite_family.GPU_VARIANTS:
+            out.append((f"rewrite_{key}@{variant}", {}, False))
     for n in ("doublePendulum", "twoBody", "spring", "threeBodyPolar", "pendulum", "chain8", "chain16"):
         out.append((n, {"HAMK_TRIG_LUT": "0"}, False))
         out.append((n, {"HAMK_TRIG_LUT": "1"}, False))
@@ -106,6 +112,10 @@ def build(job):
         elif name.startswith("symfam"):
             import symbolic_family
             spec = symbolic_family.spec(int(name[6:]))
+        elif name.startswith("rewrite_"):
+            import rewrite_family
+            key, variant = name[8:].split("@")
+            return name, env, api.system_from_spec(rewrite_family.spec(key), rewrite_family.gpu_options(variant)).code_size
         else:
             spec = examples.get(name)
         s = api.system_from_spec(spec)
