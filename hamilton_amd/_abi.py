@@ -52,7 +52,7 @@ class HamkOptions(ctypes.Structure):
                 ("gsl_api", ctypes.c_int32), ("self_check", ctypes.c_int32), ("build", ctypes.c_int32),
                 ("rk4_min_waves", ctypes.c_int32), ("k_reassoc", ctypes.c_int32),
                 ("rk4_park", ctypes.c_int32), ("max_substeps", ctypes.c_int32), ("cache", ctypes.c_int32),
-                ("lanes_per_trajectory", ctypes.c_int32), ("rkf_park", ctypes.c_int32), ("_align", ctypes.c_int32),
+                ("lanes_per_trajectory", ctypes.c_int32), ("rkf_park", ctypes.c_int32), ("step_const_vgpr", ctypes.c_int32),
                 ("ensemble_size", ctypes.c_int64), ("reserved", ctypes.c_int32 * 12)]
 
     def __init__(self, **kw):
@@ -60,12 +60,12 @@ class HamkOptions(ctypes.Structure):
         self.size = ctypes.sizeof(HamkOptions)
         self.version = OPTIONS_VERSION
         for k, v in kw.items():
-            if k not in dict(self._fields_) or k in ("size", "version", "reserved", "_align"):
+            if k not in dict(self._fields_) or k in ("size", "version", "reserved"):
                 raise TypeError(f"hamk_options has no field {k!r}")
             setattr(self, k, int(v))
 
     def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("size", "version", "reserved", "_align")}
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("size", "version", "reserved")}
 
 
 # name -> (restype, argtypes); mirrors include/hamk.h declaration by declaration

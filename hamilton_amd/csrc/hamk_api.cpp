@@ -345,6 +345,7 @@ int hamk_system_get_options(hamk_system* s, int64_t B, hamk_options* r) {
   r->rk4_min_waves = d.rk4_min_waves;
   r->k_reassoc = d.k_reassoc ? HAMK_ON : HAMK_OFF;
   r->rk4_park = d.rk4_park ? HAMK_ON : HAMK_OFF;
+  r->step_const_vgpr = (d.step_const_vgpr && d.mapping == HAMK_MAP_LANE && d.use_lut == 2) ? HAMK_ON : HAMK_OFF;
   r->rkf_park = d.rkf_park ? HAMK_ON : HAMK_OFF;
   r->max_substeps = s->max_substeps;
   r->cache = s->cache_on ? HAMK_ON : HAMK_OFF;

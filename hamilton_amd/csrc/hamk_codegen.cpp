@@ -763,7 +763,17 @@ void poly_sweep(const std::vector<hamk_op>& ops, int n, const std::vector<Poly>&
 
 // A polynomial as ONE expression over q[], v[], tc.s[], tc.c[]: the sum of its monomials, each with its own coefficient; only + * ( )
 // and hex-float literals (HIP's default contraction makes the FMAs), no temporaries -- tests parse this text.
-struct PolyNames { int n = 0, vbase = 1 << 30; };            // variable ids: q below n, v from vbase, sincos pairs in between
+// park: coefficients that no gfx950 instruction takes inline are named gk[i] instead (the parked forms mass_matrix_sym_k / gU_sym_k:
+// the caller's StepK holds them in vector registers, hamk_device.hpp), collected in *park in order of first use
+struct PolyNames { int n = 0, vbase = 1 << 30; std::vector<double>* park = nullptr; };   // variable ids: q below n, v from vbase, sincos pairs in between
+static bool inline_operand(double c) { const double a = std::fabs(c); return a == 0.0 || a == 0.5 || a == 1.0 || a == 2.0 || a == 4.0; }
+static std::string poly_coeff(double c, const PolyNames& nm) {
+  if (!nm.park || inline_operand(c)) return lit(c);
+  size_t i = 0;
+  while (i < nm.park->size() && std::memcmp(&(*nm.park)[i], &c, sizeof c) != 0) ++i;
+  if (i == nm.park->size()) nm.park->push_back(c);
+  return "gk[" + std::to_string(i) + "]";
+}
 static std::string poly_expr(const Poly& p, const PolyNames& nm) {
   std::ostringstream x;
   bool first = true;
@@ -780,9 +790,9 @@ static std::string poly_expr(const Poly& p, const PolyNames& nm) {
       }
     if (!first) x << " + ";
     first = false;
-    if (unit) x << lit(t.second);
+    if (unit) x << poly_coeff(t.second, nm);
     else if (t.second == 1.0) x << f.str();
-    else x << lit(t.second) << " * " << f.str();
+    else x << poly_coeff(t.second, nm) << " * " << f.str();
   }
   if (first) x << "0.0";
   return x.str();
@@ -968,6 +978,36 @@ void emit_symbolic_k(std::ostringstream& o, const SymK& sk) {
     }
   o << "  }\n";
 }
+// The parked forms of the two (HAMK_STEP_CONST_VGPR): the same sums, term for term, with the coefficients that would be copied once per
+// use inside the stepping loop read from gk[] -- grad U's, which meet the shared dT/dq in a two-address v_fmac, and for n = 2 the
+// constant entries of K, addends of the adjugate solve's determinant (not beyond: LDL^T takes the reciprocal of a constant pivot at
+// compile time, which an opaque register would move to run time).  mass_matrix_sym / gU_sym stay as they are, for every other caller.
+void emit_symbolic_parked(std::ostringstream& o, const SymK& sk, bool gu, std::vector<double>& park) {
+  const int n = sk.n;
+  PolyNames nm; nm.n = n; nm.park = &park;
+  PolyNames plain; plain.n = n;
+  o << "  template <class TC, class GK> __device__ __forceinline__ static void mass_matrix_sym_k(const double (&q)[N], const TC& tc, const GK& gk, double (&K)[N][N]) {\n";
+  // (two constant diagonal entries: the compiler may multiply them when it builds the module, rounding the product before the
+  // determinant's subtraction where the FMA on parked operands does not -- parked only where that product is exact)
+  auto constant_entry = [&](size_t at) { return sk.k[at].size() == 1 && sk.k[at].begin()->first.empty(); };
+  bool park_k = n == 2;
+  if (park_k && constant_entry(0) && constant_entry(2)) {
+    const double c0 = sk.k[0].begin()->second, c1 = sk.k[2].begin()->second;
+    park_k = std::fma(c0, c1, -(c0 * c1)) == 0.0;
+  }
+  size_t e = 0;
+  for (int a = 0; a < n; ++a)
+    for (int b = a; b < n; ++b, ++e) {
+      const bool constant = park_k && constant_entry(e);
+      o << "    K[" << a << "][" << b << "] = " << poly_expr(sk.k[e], constant ? nm : plain) << ";\n";
+      if (a != b) o << "    K[" << b << "][" << a << "] = K[" << a << "][" << b << "];\n";
+    }
+  o << "  }\n";
+  if (!gu) return;
+  o << "  template <class TC, class GK> __device__ __forceinline__ static void gU_sym_k(const double (&q)[N], const TC& tc, const GK& gk, double (&gU)[N]) {\n";
+  for (int i = 0; i < n; ++i) o << "    gU[" << i << "] = " << poly_expr(sk.gU[(size_t)i], nm) << ";\n";
+  o << "  }\n";
+}
 }  // namespace
 
 // Will a lane module of this system take K and dT/dq from the symbolic mass matrix?  (hamk_dispatch.cpp make_desc: such a right-hand
@@ -984,8 +1024,10 @@ bool symbolic_rhs_applies(const SystemDesc& d0) {
 }
 
 std::string generate_source(const SystemDesc& d) {
-  std::ostringstream o;
-  o << "// generated by libhamk (hamk_codegen.cpp) from the expression tape of one System " << d.m << " " << d.n << "\n";
+  std::ostringstream head, o;                               // head: what is only known once the body is written, and has to precede it
+  std::string park_list;
+  int park_n = 0;
+  head << "// generated by libhamk (hamk_codegen.cpp) from the expression tape of one System " << d.m << " " << d.n << "\n";
   if (d.rk4_min_waves > 1 || d.wave) o << "#define HAMK_RK4_MIN_WAVES " << d.rk4_min_waves << "\n#define HAMK_RK4_MIN_WAVES_BIG " << d.rk4_min_waves << "\n";
   if (d.wave && d.n > 32 && d.rk4_min_waves > 1) o << "#define HAMK_RKF_MIN_WAVES " << d.rk4_min_waves << "\n";
   o << "#define HAMK_USE_LUT " << d.use_lut << "\n";
@@ -993,6 +1035,8 @@ std::string generate_source(const SystemDesc& d) {
   if (d.rk4_park && !d.wave) o << "#define HAMK_RK4_PARK 1\n";
   if (d.mapping == HAMK_MAP_QUAD) o << "#define HAMK_QUAD_RKF_PARK " << (d.rkf_park ? 1 : 0) << "\n";
   if (d.mapping == HAMK_MAP_LANE && d.trig_const_vgpr && d.use_lut != 0) o << "#define HAMK_TRIG_CONST_VGPR 1\n";
+  const bool step_const_vgpr = d.mapping == HAMK_MAP_LANE && d.step_const_vgpr && d.use_lut == 2;
+  if (step_const_vgpr) o << "#define HAMK_STEP_CONST_VGPR 1\n";
   if (d.mapping == HAMK_MAP_LANE && d.pair_rows) o << "#define HAMK_PAIR_ROWS 1\n";
   if (d.mapping == HAMK_MAP_LANE && d.rkf_two_waves)
     o << "#define HAMK_RKF_MIN_WAVES_LANE 2\n#define HAMK_RKF_LDS_BUDGET 36\n#define HAMK_RKF_ROWS_IN_REGS 1\n";
@@ -1135,12 +1179,24 @@ std::string generate_source(const SystemDesc& d) {
     o << "  static constexpr bool HAS_SYM_GU = " << (gu ? "true" : "false") << ";\n";
     if (gu) emit_symbolic_gu(o, sk);
     else o << "  template <class TC> __device__ __forceinline__ static void gU_sym(const double (&)[N], const TC&, double (&)[N]) {}\n";
+    // the stepping loop's constants in vector registers (hamk_device.hpp StepK): the parked forms, where they stay within a handful of registers
+    if (step_const_vgpr && sk.ok) {
+      std::ostringstream pk;
+      std::vector<double> park;
+      emit_symbolic_parked(pk, sk, gu, park);
+      if (!park.empty() && park.size() <= 6) {
+        o << pk.str();
+        for (size_t i = 0; i < park.size(); ++i) park_list += (i ? ", " : "") + lit(park[i]);
+        park_n = (int)park.size();
+      }
+    }
   }
   o << "  static constexpr int NTRIG_F = " << ntrig_f << ";\n";
   o << "  static constexpr int NTRIG_U = " << ntrig_u << ";\n";
   o << "};\n\n";
   o << (d.wave ? "HAMK_INSTANTIATE_WAVE(HamkSys)\n" : (quad ? "HAMK_INSTANTIATE_QUAD(HamkSys)\n" : "HAMK_INSTANTIATE(HamkSys)\n"));
-  return o.str();
+  if (park_n > 0) head << "#define HAMK_GEN_PARK_N " << park_n << "\n#define HAMK_GEN_PARK_LIST " << park_list << "\n";
+  return head.str() + o.str();
 }
 
 }  // namespace hamk_host

@@ -517,6 +517,46 @@ struct LutLiterals {                                      // the same numbers as
                           s5 = 8.33333333333333321769e-03, s3 = -1.66666666666666657415e-01, c6 = -1.38888888888888894189e-03,
                           c4 = 4.16666666666666643537e-02, lim = 1.6e6;
 };
+// The stepping loop's own fp64 constants in VECTOR registers (HAMK_STEP_CONST_VGPR, set by the generator for the small lane kernels
+// that rotate: StageTrig::on).  A VOP3 instruction of gfx950 reads ONE scalar register pair and no 64-bit literal, so wherever a
+// constant is the ADDEND of an FMA whose multiplier is a scalar too -- the first Horner step fma(C1, z, C2) of a rotation, s3 / c4 of
+// sincos_lut_fast, the constant entries of the symbolic K in the determinant -- or is multiplied into a value that has a second reader
+// (the generated grad U coefficients next to the shared dT/dq), the compiler copies: the constant into a vector register, or the
+// shared value into the destination of a two-address v_fmac, once per use and step.  The shipped kernels, whose slow-path branches
+// leave them short of scalar registers, keep the LATER Horner addends in vector registers as well and copy each into the accumulator
+// of a v_fmac (doublePendulum: 21 v_mov_b64 among the 295 VALU instructions of a healthy lane's step; 2 of 274 with every addend
+// parked, 12 of 284 with the first steps' alone).  StepK holds those constants; rk4_body parks them once per launch behind LutK's
+// opaque statement -- an addend the compiler cannot see through stays a third operand -- everywhere else they are the literals they
+// were (an unparked StepK folds away).  Same operands, same order, same fused form: the bits do not change (tests/test_gpu_step_copies_bits.py).
+#ifndef HAMK_STEP_CONST_VGPR
+#define HAMK_STEP_CONST_VGPR 0
+#endif
+#ifndef HAMK_GEN_PARK_N                                   /* constants of the generated right-hand side that are parked with them */
+#define HAMK_GEN_PARK_N 0
+#define HAMK_GEN_PARK_LIST 0.0
+#endif
+struct RotLiterals {                                      // rotate_pair's Horner addends: the first step of <INCR_NARROW> (n_*), then s5 / c6 (h_*: <INCR_SHORT>'s first) and s3 / c4 (m_*)
+  static constexpr double n_s = -1.98412698298579493134e-04, n_c = 2.48015872894767294178e-05,
+                          h_s = 8.33333333332248946124e-03, h_c = -1.38888888888741095749e-03,
+                          m_s = -1.66666666666666324348e-01, m_c = 4.16666666666666019037e-02;
+};
+
+struct StepK {
+  double n_s = RotLiterals::n_s, n_c = RotLiterals::n_c, h_s = RotLiterals::h_s, h_c = RotLiterals::h_c;
+  double s3 = LutLiterals::s3, c4 = LutLiterals::c4;      // sincos_lut_fast
+  double m_s = RotLiterals::m_s, m_c = RotLiterals::m_c;
+  double gk[HAMK_GEN_PARK_N > 0 ? HAMK_GEN_PARK_N : 1] = {HAMK_GEN_PARK_LIST};
+  HAMK_DEV void park() {                                  // once, before the stepping loop
+    n_s = LutK::park_const(n_s); n_c = LutK::park_const(n_c); h_s = LutK::park_const(h_s); h_c = LutK::park_const(h_c);
+    s3 = LutK::park_const(s3); c4 = LutK::park_const(c4);
+    m_s = LutK::park_const(m_s); m_c = LutK::park_const(m_c);
+#pragma unroll
+    for (int i = 0; i < HAMK_GEN_PARK_N; ++i) gk[i] = LutK::park_const(gk[i]);
+  }
+};
+struct LutStepK : LutLiterals {                           // sincos_lut's literals with s3 / c4 from a StepK
+  double s3, c4;
+};
 template <class KC> HAMK_DEV void sincos_lut_fast(double x, double& s, double& c, const KC& kc) {     // |x| < 1.6e6
   const double k = rint(x * kc.inv_step);
   double r = fma(-k, kc.w0, x);
@@ -546,8 +586,13 @@ template <class KC> HAMK_DEV void sincos_lut(double x, double& s, double& c, con
 }
 HAMK_DEV void sincos_lut(double x, double& s, double& c) { sincos_lut(x, s, c, LutLiterals()); }
 // the constants a sincos site takes: the cache's own (TrigCache with HAMK_TRIG_CONST_VGPR) or the literals
+template <class TC> HAMK_DEV auto lut_consts_step(const TC& tc, int) -> decltype(tc.sk.s3, LutStepK()) { LutStepK k; k.s3 = tc.sk.s3; k.c4 = tc.sk.c4; return k; }
+template <class TC> HAMK_DEV LutLiterals lut_consts_step(const TC&, long) { return LutLiterals(); }
 template <class TC> HAMK_DEV auto lut_consts(const TC& tc, int) -> decltype(tc.kc) { return tc.kc; }
-template <class TC> HAMK_DEV LutLiterals lut_consts(const TC&, long) { return LutLiterals(); }
+template <class TC> HAMK_DEV auto lut_consts(const TC& tc, long) -> decltype(lut_consts_step(tc, 0)) { return lut_consts_step(tc, 0); }
+// ... and a rotation: the cache's StepK (HAMK_STEP_CONST_VGPR) or the literals
+template <class TC> HAMK_DEV auto rot_consts(const TC& tc, int) -> decltype((tc.sk)) { return tc.sk; }
+template <class TC> HAMK_DEV RotLiterals rot_consts(const TC&, long) { return RotLiterals(); }
 
 // sin and cos of one argument always come as a pair (codegen fuses the tape's
 // SIN/COS of a shared operand): one fp64 sincos feeds value, gradient and Hessian.
@@ -596,6 +641,9 @@ template <int NS> struct TrigCache {
 #if HAMK_TRIG_CONST_VGPR
   LutK kc;                                                                 // sincos_lut's literals, in vector registers (see LutK)
 #endif
+#if HAMK_STEP_CONST_VGPR
+  StepK sk;                                                                // the stepping loop's addend constants (see StepK): literals until parked
+#endif
   HAMK_DEV TrigCache() {                                                   // a defined anchor (0, sin 0, cos 0) from the start
 #pragma unroll
     for (int k = 0; k < (NS > 0 ? NS : 1); ++k) { ax[k] = 0.0; as[k] = 0.0; ac[k] = 1.0; }
@@ -608,7 +656,7 @@ enum : int { INCR_WIDE = 0, INCR_NARROW = 1, INCR_SHORT = 2 };
 template <int RANGE> HAMK_DEV constexpr double incr_limit() {
   return (RANGE == INCR_WIDE) ? 0.25 : ((RANGE == INCR_NARROW) ? 0.125 : 0.03125);
 }
-template <int RANGE> HAMK_DEV void rotate_pair(double d, double sa, double ca, double& s, double& c) {
+template <int RANGE, class RK = RotLiterals> HAMK_DEV void rotate_pair(double d, double sa, double ca, double& s, double& c, const RK& rk = RK()) {
 #if HAMK_ROTATE_HORNER
   // Horner form: one FMA per coefficient and no powers of z -- fewer instructions, a longer dependent chain.  The kernels that
   // rotate are the small systems' (1-4 sincos sites), which run several wavefronts per SIMD and are bound by VALU ISSUE, not by
@@ -626,17 +674,17 @@ template <int RANGE> HAMK_DEV void rotate_pair(double d, double sa, double ca, d
     pc = fma(2.08757232129817482790e-09, z, -2.75573143513906633035e-07);
     pc = fma(pc, z, 2.48015872894767294178e-05);
   } else if constexpr (RANGE == INCR_NARROW) {
-    ps = fma(2.75573137070700676789e-06, z, -1.98412698298579493134e-04);
-    pc = fma(-2.75573143513906633035e-07, z, 2.48015872894767294178e-05);
+    ps = fma(2.75573137070700676789e-06, z, rk.n_s);      // (rk: the addends, literals or parked -- see StepK)
+    pc = fma(-2.75573143513906633035e-07, z, rk.n_c);
   } else {
     ps = -1.98412698298579493134e-04;
     pc = 2.48015872894767294178e-05;
   }
-  ps = fma(ps, z, 8.33333333332248946124e-03);
-  ps = fma(ps, z, -1.66666666666666324348e-01);
+  ps = fma(ps, z, rk.h_s);
+  ps = fma(ps, z, rk.m_s);
   const double sd = fma(d * z, ps, d);                    // sin(d)
-  pc = fma(pc, z, -1.38888888888741095749e-03);
-  pc = fma(pc, z, 4.16666666666666019037e-02);
+  pc = fma(pc, z, rk.h_c);
+  pc = fma(pc, z, rk.m_c);
   pc = fma(pc, z, -0.5);
   const double cm1 = z * pc;                              // cos(d) - 1
   s = fma(ca, sd, fma(sa, cm1, sa));
@@ -710,8 +758,8 @@ template <int MODE, class TC> HAMK_DEV void trig_pair(double x, TC& tc, int k) {
     bool full = true;
     if (mode != DYN_FULL_ANCHOR) {
       const double d = x - tc.ax[k];
-      if (mode == DYN_SHORT) { rotate_pair<INCR_SHORT>(d, tc.as[k], tc.ac[k], tc.s[k], tc.c[k]); full = !(fabs(d) < incr_limit<INCR_SHORT>()); }
-      else { rotate_pair<INCR_NARROW>(d, tc.as[k], tc.ac[k], tc.s[k], tc.c[k]); full = !(fabs(d) < incr_limit<INCR_NARROW>()); }
+      if (mode == DYN_SHORT) { rotate_pair<INCR_SHORT>(d, tc.as[k], tc.ac[k], tc.s[k], tc.c[k], rot_consts(tc, 0)); full = !(fabs(d) < incr_limit<INCR_SHORT>()); }
+      else { rotate_pair<INCR_NARROW>(d, tc.as[k], tc.ac[k], tc.s[k], tc.c[k], rot_consts(tc, 0)); full = !(fabs(d) < incr_limit<INCR_NARROW>()); }
     }
     // (with the LDS table loaded -- HAMK_USE_LUT -- the full evaluation is sincos_lut: 20 instructions)
 #ifdef HAMK_PROBE_NO_SLOWPATH
@@ -1136,6 +1184,14 @@ template <class S, class TC> HAMK_DEV void trig_burst_lut(const double (&q)[S::N
 #endif
 }
 
+// The generator's symbolic K and grad U: their parked forms where the module has them and the cache carries a StepK (HAMK_STEP_CONST_VGPR)
+template <class S, class TC> HAMK_DEV auto sym_mass_matrix(const double (&q)[S::N], const TC& tc, double (&K)[S::N][S::N], int)
+    -> decltype(S::mass_matrix_sym_k(q, tc, tc.sk.gk, K)) { S::mass_matrix_sym_k(q, tc, tc.sk.gk, K); }
+template <class S, class TC> HAMK_DEV void sym_mass_matrix(const double (&q)[S::N], const TC& tc, double (&K)[S::N][S::N], long) { S::mass_matrix_sym(q, tc, K); }
+template <class S, class TC> HAMK_DEV auto sym_grad_u(const double (&q)[S::N], const TC& tc, double (&gU)[S::N], int)
+    -> decltype(S::gU_sym_k(q, tc, tc.sk.gk, gU)) { S::gU_sym_k(q, tc, tc.sk.gk, gU); }
+template <class S, class TC> HAMK_DEV void sym_grad_u(const double (&q)[S::N], const TC& tc, double (&gU)[S::N], long) { S::gU_sym(q, tc, gU); }
+
 template <class S, bool MODE_H, int TRIG_IN = TRIG_FULL, bool BURST_OK = true>
 HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (&dq)[S::N], double (&dp)[S::N], int& st,
                       TrigCache<S::NTRIG_F>& tc) {
@@ -1149,9 +1205,9 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
     // evaluated in plain doubles, only to fill the sincos pairs
     double x[M];
     S::template coords<double, TRIG>(q, x, tc);
-    S::mass_matrix_sym(q, tc, K);
+    sym_mass_matrix<S>(q, tc, K, 0);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
-    S::gU_sym(q, tc, gU);
+    sym_grad_u<S>(q, tc, gU, 0);
     S::dT_sym(q, v, tc, dT);
   } else if constexpr (S::HAS_SYM_K && S::HAS_SYM_DT) {
     // K and dT/dq = -1/2 v^T (dK/dq) v from the generator's symbolic mass matrix (hamk_codegen.cpp symbolic_mass_matrix): the
@@ -1159,7 +1215,7 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
     Jet1<N> qj[N], xj[M];
     seed1<S>(q, qj);
     S::template coords<Jet1<N>, TRIG>(qj, xj, tc);
-    S::mass_matrix_sym(q, tc, K);
+    sym_mass_matrix<S>(q, tc, K, 0);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
     double U;
     grad_potential<S>(qj, xj, gU, U, tc);
@@ -1180,7 +1236,7 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
 #pragma unroll
       for (int i = 0; i < N; ++i) xj[k].d[i] = xh[k].d[i];
     }
-    if constexpr (S::HAS_SYM_K) S::mass_matrix_sym(q, tc, K); else mass_matrix<S>(xj, K);
+    if constexpr (S::HAS_SYM_K) sym_mass_matrix<S>(q, tc, K, 0); else mass_matrix<S>(xj, K);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
     double U;
     grad_potential<S>(qj, xj, gU, U, tc);
@@ -1204,7 +1260,7 @@ HAMK_DEV void ham_eqs(const double (&q)[S::N], const double (&p)[S::N], double (
     Jet1<N> qj[N], xj[M];
     seed1<S>(q, qj);
     S::template coords<Jet1<N>, TRIG>(qj, xj, tc);
-    if constexpr (S::HAS_SYM_K) S::mass_matrix_sym(q, tc, K); else mass_matrix<S>(xj, K);
+    if constexpr (S::HAS_SYM_K) sym_mass_matrix<S>(q, tc, K, 0); else mass_matrix<S>(xj, K);
     solve_spd<N, S::INERTIA_POS>(K, p, v, st);
     double U;
     grad_potential<S>(qj, xj, gU, U, tc);
@@ -1281,6 +1337,15 @@ HAMK_DEV void rhs(const double (&y)[2 * S::N], double (&dy)[2 * S::N], int& st, 
   for (int i = 0; i < N; ++i) { dy[i] = dq[i]; dy[N + i] = dp[i]; }
 }
 
+// a reader of x that emits nothing: x is alive up to here
+HAMK_DEV void keep_alive(double x) {
+#ifndef HAMK_HOST_EMULATION
+  asm volatile("" : : "v"(x));
+#else
+  (void)x;
+#endif
+}
+
 // ---- NaN/Inf test on raw bits: immune to -fno-honor-nans folding -------------
 HAMK_DEV bool is_nonfinite_bits(double x) {
   unsigned int hi = (unsigned int)__double2hiint(x);
@@ -1330,6 +1395,9 @@ HAMK_DEV void rk4_body(double* __restrict__ q, double* __restrict__ p, i64 B, do
   const double h2 = 0.5 * dt, h6 = dt * (1.0 / 6.0), h3 = dt * (1.0 / 3.0);
   double H0 = 0.0;
   if (drift_tol > 0.0) H0 = energy<S>(y, st);
+#if HAMK_STEP_CONST_VGPR
+  if constexpr (StageTrig<S>::on) tc.sk.park();             // the loop's addend constants into vector registers, once per launch (StepK)
+#endif
   if constexpr (S::RK4_STAGE_LOOP && HAMK_RK4_PARK) {
     // Large systems (n = 12..16): one right-hand side alone needs ~500 of the 512 registers a lane can have (K is
     // n(n+1)/2 doubles), so the 2 x 2n doubles that only wait across it -- the step's base point y and the running
@@ -1415,8 +1483,16 @@ HAMK_DEV void rk4_body(double* __restrict__ q, double* __restrict__ p, i64 B, do
       for (int j = 0; j < D; ++j) { acc[j] = fma(h3, k[j], acc[j]); yt[j] = fma(dt, k[j], y[j]); }
       tc.mode = DYN_NARROW;
       rhs<S, StageTrig<S>::dyn, StageTrig<S>::burst_rk4>(yt, k, st, tc);
+#if HAMK_STEP_CONST_VGPR
+      // acc stays alive one (empty) statement past the step's last combination: with the accumulator dying in it the compiler takes
+      // the two-address v_fmac into acc's register and copies the result back into y's, one v_mov_b64 per component and step;
+      // with a later reader it takes the three-address v_fma_f64 straight into y's register
+#pragma unroll
+      for (int j = 0; j < D; ++j) { y[j] = fma(h6, k[j], acc[j]); keep_alive(acc[j]); }
+#else
 #pragma unroll
       for (int j = 0; j < D; ++j) y[j] = fma(h6, k[j], acc[j]);
+#endif
     }
   }
   if (drift_tol > 0.0) {

@@ -409,7 +409,7 @@ std::string check_options(const hamk_options& o, int n) {
   if (!in(o.trig, {HAMK_AUTO, HAMK_TRIG_DIRECT, HAMK_TRIG_TABLE, HAMK_TRIG_TABLE_ROTATE})) return "trig must be HAMK_AUTO or a HAMK_TRIG_* value";
   if (!in(o.gsl_api, {HAMK_AUTO, 1, 2})) return "gsl_api must be HAMK_AUTO, 1 (gsl_odeiv) or 2 (gsl_odeiv2)";
   if (!in(o.build, {HAMK_AUTO, HAMK_BUILD_DEFAULT, HAMK_BUILD_NOLICM})) return "build must be HAMK_AUTO or a HAMK_BUILD_* value";
-  for (int v : {o.self_check, o.k_reassoc, o.rk4_park, o.rkf_park, o.cache})
+  for (int v : {o.self_check, o.k_reassoc, o.rk4_park, o.rkf_park, o.cache, o.step_const_vgpr})
     if (!in(v, {HAMK_AUTO, HAMK_ON, HAMK_OFF})) return "switches must be HAMK_AUTO, HAMK_ON or HAMK_OFF";
   if (o.rk4_min_waves < 0 || o.rk4_min_waves > 8) return "rk4_min_waves must be 0 (auto) .. 8";
   if (o.max_substeps < 0) return "max_substeps must be >= 0";
@@ -604,6 +604,11 @@ static SystemDesc make_desc(const hamk_system* s, int mapping, bool* forced_rk4,
   // -6 % / -6 % (18 more registers where occupancy pays) -- so: 8 <= n <= 14.
   d.trig_const_vgpr = mapping == HAMK_MAP_LANE && n >= 8 && n <= 14;
   if (env_flag("HAMK_TRIG_CONST_VGPR", &b)) d.trig_const_vgpr = b && mapping == HAMK_MAP_LANE;      // test override (the rule above was measured on the chains)
+  // the stepping loop's addend constants in vector registers (hamk_device.hpp StepK; the generator applies it where the kernel rotates):
+  // on; OFF / HAMK_STEP_CONST_VGPR=0 builds the form without, for the A/B and tests/test_gpu_step_copies_bits.py
+  d.step_const_vgpr = mapping == HAMK_MAP_LANE;
+  if (o.step_const_vgpr != HAMK_AUTO) d.step_const_vgpr = o.step_const_vgpr == HAMK_ON && mapping == HAMK_MAP_LANE;
+  else if (env_flag("HAMK_STEP_CONST_VGPR", &b)) d.step_const_vgpr = b && mapping == HAMK_MAP_LANE;
   if (o.trig != HAMK_AUTO) d.use_lut = o.trig == HAMK_TRIG_DIRECT ? 0 : (o.trig == HAMK_TRIG_TABLE ? 1 : 2);
   else if (const char* e = test_env("HAMK_TRIG_LUT")) { if (e[0] >= '0' && e[0] <= '2') d.use_lut = e[0] - '0'; }
   derive_body_fields(s, d);

@@ -27,6 +27,7 @@ struct SystemDesc {
   bool rkf_park = false;        // lane / quad mapping: the RKF45 stepper's vectors in a run-time-indexed private array
   bool rk4_park = false;        // lane mapping: RK4 stage loop parks y / acc in LDS across the right-hand side
   bool trig_const_vgpr = false; // lane mapping, 8 <= n <= 14: sincos_lut's fp64 literals live in vector registers (hamk_device.hpp LutK)
+  bool step_const_vgpr = true;  // lane mapping, kernels that rotate (use_lut == 2): the stepping loop's addend constants live in vector registers (hamk_device.hpp StepK)
   bool rkf_two_waves = false;   // lane mapping, n <= 7: the parked RKF45 stepper at two wavefronts per SIMD (rows beyond a halved LDS share in registers)
   bool pair_rows = false;       // lane mapping, n = 8, 9: the parked stepper's LDS rows hold components in pairs (16-byte accesses; hamk_device.hpp HAMK_PAIR_ROWS)
   bool quad_dense = false;      // quad mapping, a coordinate map with a dense Jacobian: K accumulated in passes (hamk_quad.hpp assemble_dense)

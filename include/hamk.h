@@ -211,7 +211,10 @@ typedef struct hamk_options {
                               for registers; AUTO: n >= 17.  Lane mapping: follows rkf_body (the stage-loop body IS the
                               parked one since round 4): reported; a value that contradicts rkf_body is refused with
                               HAMK_ERR_UNSUPPORTED when the lane specialisation is built                                 */
-  int32_t _align;          /* keeps ensemble_size 8-byte aligned; 0                                                     */
+  int32_t step_const_vgpr; /* ON | OFF: lane mapping, stepping kernels that rotate sincos pairs: the loop's addend constants (the
+                              rotations' Horner addends, the table evaluation's s3 / c4, constant entries of a symbolic 2 x 2 K, grad
+                              U's coefficients) are parked in vector registers before the loop; same bits either way; AUTO: ON.  (The
+                              slot that used to be padding in front of ensemble_size: 0 = AUTO in every older caller)          */
   int64_t ensemble_size;   /* mapping = AUTO only: the size of the WHOLE ensemble this handle's launches are pieces of (a shard
                               of a multi-GPU run, a chunk of a host loop).  AUTO picks the mapping from the ensemble size, and
                               two mappings agree to roundoff, not bitwise -- so a host that states the whole ensemble's size
