@@ -294,6 +294,8 @@ int hamk_system_create_ex(int32_t m, int32_t n, const double* inertia, const ham
   s->base.f_outs.assign(f_outs, f_outs + m);
   s->base.u_ops.assign(u_ops, u_ops + u_nops);
   s->base.u_out = u_out;
+  err = check_options(o, s->base);
+  if (!err.empty()) { hamk_system_destroy(s); return fail(HAMK_ERR_UNSUPPORTED, "hamk_options: " + err); }
   s->gsl_api = o.gsl_api ? o.gsl_api : 2;
   if (o.gsl_api == HAMK_AUTO) if (const char* e = test_env("HAMK_GSL_API")) s->gsl_api = (e[0] == '1') ? 1 : 2;
   s->self_check_on = o.self_check != HAMK_OFF;

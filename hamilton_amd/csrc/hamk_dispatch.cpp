@@ -341,6 +341,7 @@ int current_device_state(hamk_system* s) {
 
 int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out);
 std::string check_options(const hamk_options& o, int n);
+std::string check_options(const hamk_options& o, const SystemDesc& base);
 
 // Everything a call over B trajectories needs in place: the device state, the specialisation chosen for (n, B) --
 // built on first use --, its modules loaded on this device and self-checked.
@@ -417,6 +418,21 @@ std::string check_options(const hamk_options& o, int n) {
   return std::string();
 }
 
+// The four-lane kernels' dense path (hamk_quad.hpp assemble_dense) keeps dU/dx of a potential over the CARTESIAN coordinates in LDS
+// while J^T dU/dx is swept: m values in the NP4 rows of the velocities plus the NP4 rows of dU/dq (NP4 = n rounded up to a multiple of
+// four).  A map with more outputs than that does not fit; the wave-cooperative kernels serve it.
+static int quad_dense_rows(int n) { return 2 * (4 * ((n + 3) / 4)); }
+static bool quad_dense_holds(const SystemDesc& b) { return b.u_space != HAMK_U_CARTESIAN || b.m <= quad_dense_rows(b.n); }
+
+// The part of the options that depends on the system itself (the tapes are validated by now).
+std::string check_options(const hamk_options& o, const SystemDesc& base) {
+  if (o.mapping == HAMK_MAP_QUAD && distinct_jacobian_entries(base) > 8 * base.n && !quad_dense_holds(base))
+    return "unsupported: HAMK_MAP_QUAD holds a dense coordinate map under a potential over the cartesian coordinates only up to m = 2 * NP4 = " +
+           std::to_string(quad_dense_rows(base.n)) + " outputs at n = " + std::to_string(base.n) + " (dU/dx waits in 2 * NP4 rows of LDS, NP4 = n rounded up "
+           "to a multiple of four); this system has m = " + std::to_string(base.m) + " (leave the mapping to the library, or ask for HAMK_MAP_WAVE)";
+  return std::string();
+}
+
 // Which lanes serve a trajectory for an ensemble of B (hamk_options::mapping = HAMK_AUTO).
 // The lane kernels do the least work per trajectory (compile-time sparsity of the seeds, everything in registers) but
 // put 64 trajectories in a wavefront: below ~64 x 1024 SIMDs trajectories they leave SIMDs idle, and for the systems
@@ -435,16 +451,17 @@ static bool quad_eligible(hamk_system* s) {
 // Round 6: a DENSE Jacobian whose entries are cheap.  With compile-time seeds a lane evaluates J at forward_gradient_work
 // operations per sweep whatever the number of distinct entries; hamk_quad.hpp's dense path (K accumulated in passes over groups of
 // row slots, one re-evaluation of J per pass) then needs ~3 x that + n^2 m / 8 per lane for SIXTEEN trajectories per wavefront,
-// where the wave-cooperative kernels evaluate the whole tape in every lane for two.  Taken where a sweep costs at most 4 m n
+// where the wave-cooperative kernels evaluate the whole tape in every lane for two.  Not where dU/dx of a cartesian potential does not
+// fit its LDS rows (quad_dense_holds: m > 2 NP4).  Taken where a sweep costs at most 4 m n
 // (x = 2 q + A sin q + B cos q: 2 m n); a map whose operations all depend on all inputs (tape x n) stays on the wave kernels.
 // Measured on MI355X (profiles/r06_dense_quad_ab.jsonl): dense32 / dense24 RK4 steps/s on this mapping against the wave kernels'.
 static bool quad_dense_eligible(hamk_system* s) {
   if (s->quad_dense_eligible < 0) {
     const long long mn = (long long)s->base.m * s->base.n;
-    s->quad_dense_eligible = (s->base.n > 16 && s->base.n <= 32 && forward_gradient_work(s->base) <= 4 * mn) ? 1 : 0;
+    s->quad_dense_eligible = (s->base.n > 16 && s->base.n <= 32 && quad_dense_holds(s->base) && forward_gradient_work(s->base) <= 4 * mn) ? 1 : 0;
   }
   bool b = false;
-  if (env_flag("HAMK_QUAD_DENSE", &b)) return b && s->base.n > 16 && s->base.n <= 32;      // test override (A/B against the wave kernels)
+  if (env_flag("HAMK_QUAD_DENSE", &b)) return b && s->base.n > 16 && s->base.n <= 32 && quad_dense_holds(s->base);      // test override (A/B against the wave kernels)
   return s->quad_dense_eligible == 1;
 }
 

@@ -205,6 +205,7 @@ int sample_code(bool cache_on, const std::vector<char>** out);        // hamk_sa
 
 // ---- hamk_dispatch.cpp ------------------------------------------------------------------------------------------------
 std::string check_options(const hamk_options& o, int n);
+std::string check_options(const hamk_options& o, const SystemDesc& base);      // what depends on the system: the dense quad path's capacity
 int build_force(const hamk_system* s);
 int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out);
 int current_device_state(hamk_system* s);

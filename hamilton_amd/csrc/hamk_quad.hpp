@@ -640,6 +640,8 @@ HAMK_DEV void assemble_dense(const Ctx<S>& c, double (&Kp)[Geo<S::N>::NR][Geo<S:
     HAMK_QUAD_SYNC();
     dense_grad_rows<S, 0, LO>(c, tc, gUi);
     dense_grad_rows<S, LO, NR>(c, tc, gUi);
+    // the part of dU/dx that waits in the rows of GU: every lane of the quad has read it before any lane's dU/dq goes there (velocity)
+    if constexpr (M > NP4) HAMK_QUAD_SYNC();
   } else {
     double qv[N];
 #pragma unroll

@@ -57,6 +57,11 @@ def jobs():
     for key in rewrite_family.KEYS:
         for variant in rewrite_family.GPU_VARIANTS:
             out.append((f"rewrite_{key}@{variant}", {}, False))
+    # rectangular coordinate maps (tests/test_gpu_rect_family.py, tests/test_rect_family.py): the family of tests/rect_family.py, each
+    # member with the mapping its table asks for, three of them on the wave kernels as well.  The dense n >= 17 modules among them
+    # are the slowest compiles of the whole list (minutes each), so these jobs go to the FRONT of the queue (the return below)
+    import rect_family
+    rect = [(f"rect_{key}@{ask or 'auto'}", {}, False) for key, ask in rect_family.GPU_RUNS]
     for n in ("doublePendulum", "twoBody", "spring", "threeBodyPolar", "pendulum", "chain8", "chain16"):
         out.append((n, {"HAMK_TRIG_LUT": "0"}, False))
         out.append((n, {"HAMK_TRIG_LUT": "1"}, False))
@@ -82,7 +87,7 @@ def jobs():
         out.append((n, {}, False))
     out.append(("chain12", {"HAMK_QUAD": "1"}, False))
     out.append(("sampler", {}, False))
-    return out
+    return rect + out
 
 
 TESTS_ONLY = "--tests-only" in sys.argv         # tests/conftest.py: no instruction-count probe builds (bench.py's)
@@ -112,6 +117,10 @@ def build(job):
         elif name.startswith("symfam"):
             import symbolic_family
             spec = symbolic_family.spec(int(name[6:]))
+        elif name.startswith("rect_"):
+            import rect_family
+            key, ask = name[5:].split("@")
+            return name, env, api.system_from_spec(rect_family.spec(key), rect_family.options(None if ask == "auto" else ask)).code_size
         elif name.startswith("rewrite_"):
             import rewrite_family
             key, variant = name[8:].split("@")
