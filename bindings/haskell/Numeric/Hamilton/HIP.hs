@@ -46,6 +46,7 @@ module Numeric.Hamilton.HIP
   , stepHamBatch
   , iterateStepHamBatch
   , rk4StepsBatch
+  , symplecticStepsBatch
   , evolveHamEnsemble
     -- * ensembles resident in HBM, several GPUs from one process
   , DeviceEnsemble
@@ -205,6 +206,9 @@ foreign import ccall unsafe "hamk_system_set_gsl_api"
   c_set_gsl_api :: Ptr HamkSystem -> Int32 -> IO CInt
 foreign import ccall safe "hamk_rk4_steps_checked"
   c_rk4_steps_checked :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Double -> Ptr Int32 -> Int32 -> IO CInt
+foreign import ccall safe "hamk_symplectic_steps"
+  c_symplectic_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32 -> Int32 -> Ptr Double
+                     -> Ptr Int32 -> Int32 -> IO CInt
 foreign import ccall safe "hamk_checkpoint_write"
   c_ck_write :: CString -> Int32 -> Int64 -> Ptr Double -> Ptr Double -> Int32 -> Int64 -> Word64 -> Double -> IO CInt
 foreign import ccall safe "hamk_checkpoint_info"
@@ -497,6 +501,14 @@ iterateStepHamBatch r k (HipSystem h) e = withForeignPtr h $ \s ->
 rk4StepsBatch :: forall m n. KnownNat n => Double -> Int -> HipSystem m n -> Ensemble n -> IO (Ensemble n)
 rk4StepsBatch dt k (HipSystem h) e = withForeignPtr h $ \s ->
   inPlace e (\b pq pp -> c_rk4_steps s b pq pp dt (fromIntegral k) nullPtr memHost) "rk4Steps"
+
+-- | Symplectic fixed-step stepping (no counterpart in the reference): @k@ steps of @dt@ by the implicit midpoint rule
+--   (@order@ 2) or its three-substep symmetric composition (@order@ 4), @iters@ fixed-point iterations per substep
+--   (0: the library's 8).  One trajectory per lane: @n <= 16@.
+symplecticStepsBatch :: forall m n. KnownNat n => Double -> Int -> Int -> Int -> HipSystem m n -> Ensemble n -> IO (Ensemble n)
+symplecticStepsBatch dt k order iters (HipSystem h) e = withForeignPtr h $ \s ->
+  inPlace e (\b pq pp -> c_symplectic_steps s b pq pp dt (fromIntegral k) (fromIntegral order) (fromIntegral iters) nullPtr nullPtr memHost)
+    "symplecticSteps"
 
 -- | 'evolveHam' (Hamilton.hs:433-462) for every member: one ensemble per requested time,
 --   element 0 being the initial ensemble.

@@ -84,12 +84,13 @@ class _Arr:
     def mem(self):
         return MEM_DEVICE if self.device else MEM_HOST
 
-    def like(self, rows: Optional[int] = None, dtype="f8", lead: Sequence[int] = ()):
+    def like(self, rows: Optional[int] = None, dtype="f8", lead: Sequence[int] = (), zero: bool = False):
+        """An output array beside this one; zero=True where a call may legally return without writing it."""
         shape = tuple(lead) + ((rows, self.B) if rows is not None else (self.B,))
         if self.device:
             dt = torch.float64 if dtype == "f8" else torch.int32
-            return torch.empty(shape, dtype=dt, device=self.a.device)
-        return np.empty(shape, dtype=np.float64 if dtype == "f8" else np.int32)
+            return (torch.zeros if zero else torch.empty)(shape, dtype=dt, device=self.a.device)
+        return (np.zeros if zero else np.empty)(shape, dtype=np.float64 if dtype == "f8" else np.int32)
 
     def clone(self):
         return self.a.clone() if self.device else self.a.copy()
@@ -232,6 +233,27 @@ class System:
     @property
     def code_size(self) -> int:
         return int(_abi.lib().hamk_system_code_size(self._h))
+
+    def _symplectic_text(self, fn) -> str:
+        """A `const char*` return carries no code: NULL means hamk_last_error() says why.  The code of the exception is read off
+        that text -- the stepper refused for this handle (n > 16, another mapping stated: HAMK_ERR_UNSUPPORTED), else a failed
+        build of the companion module (HAMK_ERR_COMPILE)."""
+        text = fn(self._h)
+        if text is None:
+            msg = _abi.lib().hamk_last_error().decode("utf-8", "replace")
+            unsupported = msg.startswith("the symplectic stepper") or "unsupported" in msg
+            raise HamkError(_abi.HAMK_ERR_UNSUPPORTED if unsupported else _abi.HAMK_ERR_COMPILE, msg)
+        return text.decode()
+
+    @property
+    def symplectic_source(self) -> str:
+        """Source of the symplectic stepper's companion module (hamk_symplectic_source; builds it if needed, needs no GPU)."""
+        return self._symplectic_text(_abi.lib().hamk_symplectic_source)
+
+    @property
+    def symplectic_build_info(self) -> str:
+        """One `build_info`-format line for hamk_symp_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs."""
+        return self._symplectic_text(_abi.lib().hamk_symplectic_build_info)
 
     def kernel_bytes(self, kernel: str) -> int:
         return int(_abi.lib().hamk_system_kernel_bytes(self._h, kernel.encode()))
@@ -535,6 +557,28 @@ def rk4Steps(dt: float, nsteps: int, s: System, ph: Phase, inplace: bool = False
                                                      _ptr(st), qa.mem))
     s.last_status = st
     return Phase(_shape_out(q, qa.single), _shape_out(p, qa.single))
+
+
+def symplecticSteps(dt: float, nsteps: int, s: System, ph: Phase, order: int = 2, iters: int = 0, inplace: bool = False,
+                    with_residual: bool = False):
+    """Symplectic fixed-step stepping (hamk_symplectic_steps; no reference counterpart): `nsteps` steps of `dt` by the
+    implicit midpoint rule (order=2) or its three-substep symmetric composition (order=4), every substep solved by
+    `iters` fixed-point iterations (1..64; 0 = the library's 8) -- a fixed count, so cost and bits do not depend on
+    convergence.  One trajectory per lane: n <= 16.  with_residual=True returns (Phase, residual): per trajectory the
+    largest last-iteration update, the way to learn that `iters` was too small for this dt."""
+    qa, pa = _pair(ph.positions, "positions", ph.momenta, "momenta", s.n)
+    if inplace:
+        _in_place(qa, ph.positions, "positions"); _in_place(pa, ph.momenta, "momenta")
+    q, p = (qa.a, pa.a) if inplace else (qa.clone(), pa.clone())
+    # zeroed: with nothing to do (nsteps = 0, an empty ensemble) the call returns HAMK_OK without writing status / residual
+    st = qa.like(None, "i4", zero=True)
+    res = qa.like(None, zero=True) if with_residual else None
+    with s._on(qa):
+        _abi.check(_abi.lib().hamk_symplectic_steps(s._h, qa.B, _ptr(q), _ptr(p), float(dt), int(nsteps), int(order), int(iters),
+                                                    _ptr(res), _ptr(st), qa.mem))
+    s._after(st, qa.single, "symplecticSteps")
+    out = Phase(_shape_out(q, qa.single), _shape_out(p, qa.single))
+    return (out, _shape_out(res, qa.single)) if with_residual else out
 
 
 # ---------------------------------------------------------------------------------------

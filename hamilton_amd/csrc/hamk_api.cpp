@@ -753,6 +753,68 @@ int hamk_rk4_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, i
   return hamk_rk4_steps_checked(s, B, q, p, dt, nsteps, 0.0, status, mem);
 }
 
+// ---- symplectic fixed-step stepping (hamk_symp.hpp) -------------------------------------------------------------------
+// The lane variant of a handle that can run the stepper, its companion module built: n <= 16 and no other mapping stated.
+// AUTO never leaves the lane mapping here, whatever B is (its small-ensemble rule for 11 <= n <= 16 was measured on RK4).
+static int symp_variant(hamk_system* s, Variant** out) {
+  if (s->base.n > 16)
+    return fail(HAMK_ERR_UNSUPPORTED, "the symplectic stepper runs one trajectory per lane: n <= 16 (this system has n = " + std::to_string(s->base.n) + ")");
+  if (s->opt.mapping == HAMK_MAP_QUAD || s->opt.mapping == HAMK_MAP_WAVE)
+    return fail(HAMK_ERR_UNSUPPORTED, std::string("the symplectic stepper runs one trajectory per lane (n <= 16, HAMK_MAP_LANE): this handle's options state ") +
+                                          (s->opt.mapping == HAMK_MAP_QUAD ? "HAMK_MAP_QUAD" : "HAMK_MAP_WAVE"));
+  TRY(lane_variant(s, out));
+  return build_symp(*out, s->cache_on);
+}
+
+const char* hamk_symplectic_source(hamk_system* s) {
+  Variant* v = nullptr;
+  if (!s) { fail(HAMK_ERR_INVALID, "null system handle"); return nullptr; }
+  return symp_variant(s, &v) == HAMK_OK ? v->symp_source.c_str() : nullptr;
+}
+
+const char* hamk_symplectic_build_info(hamk_system* s) {
+  Variant* v = nullptr;
+  if (!s) { fail(HAMK_ERR_INVALID, "null system handle"); return nullptr; }
+  return symp_variant(s, &v) == HAMK_OK ? v->symp_info.c_str() : nullptr;
+}
+
+int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t order,
+                          int32_t iters, double* residual, int32_t* status, int32_t mem) {
+  TRY(check_call(s, B, mem));
+  if (!q || !p) return fail(HAMK_ERR_INVALID, "null q / p");
+  if (nsteps < 0) return fail(HAMK_ERR_INVALID, "negative nsteps");
+  if (order != 2 && order != 4) return fail(HAMK_ERR_INVALID, "order must be 2 (implicit midpoint) or 4 (its three-substep composition)");
+  if (iters < 0 || iters > 64) return fail(HAMK_ERR_INVALID, "iters must be 1 .. 64, or HAMK_AUTO (8)");
+  if (!std::isfinite(dt)) return fail(HAMK_ERR_INVALID, "dt is not finite");
+  Variant* v = nullptr;
+  TRY(symp_variant(s, &v));
+  if (B == 0 || nsteps == 0) return HAMK_OK;
+  TRY(current_device_state(s));
+  DevModule& m = s->cur->mod[HAMK_MAP_LANE];
+  if (!m.symp_fn) {
+    if (m.symp_module) { hipModuleUnload(m.symp_module); m.symp_module = nullptr; }
+    HIP_TRY(hipModuleLoadData(&m.symp_module, v->symp_code.data()));
+    HIP_TRY(hipModuleGetFunction(&m.symp_fn, m.symp_module, "hamk_symp_steps_k"));
+  }
+  // order 4: substeps g1 dt, g2 dt, g1 dt with g1 = 1 / (2 - 2^(1/3)), g2 = 1 - 2 g1 (negative: the middle substep goes back)
+  const double g1 = 1.0 / (2.0 - std::pow(2.0, 1.0 / 3.0)), g2 = 1.0 - 2.0 * g1;
+  double ha = order == 4 ? g1 * dt : dt, hb = order == 4 ? g2 * dt : 0.0;
+  int nsub = order == 4 ? 3 : 1, ns = nsteps, it = iters == HAMK_AUTO ? 8 : iters;
+  const int64_t grid = (B + 255) / 256;
+  if (grid > 0x7fffffffLL) return fail(HAMK_ERR_INVALID, "ensemble too large for one launch");
+  Stager st(s, mem);
+  const size_t cnt = (size_t)s->base.n * B;
+  double *xq, *xp, *xr; int32_t* dst;
+  TRY(st.inout(q, cnt, &xq));
+  TRY(st.inout(p, cnt, &xp));
+  TRY(st.out(residual, (size_t)B, &xr));
+  TRY(st.out(status, (size_t)B, &dst));
+  long long b = B;
+  void* args[] = {&xq, &xp, &b, &ns, &nsub, &ha, &hb, &it, &xr, &dst};
+  HIP_TRY(hipModuleLaunchKernel(m.symp_fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, s->cur->stream, args, nullptr));
+  return st.finish();
+}
+
 static int upload_times(hamk_system* s, int32_t nt, const double* ts) {
   if ((size_t)nt > s->cur->d_ts_cap) {
     if (s->cur->d_ts) hipFree(s->cur->d_ts);

@@ -37,6 +37,9 @@ static const char kQuadHeader[] =
 static const char kSampleSource[] =
 #include "hamk_sample_src.inc"
     ;
+static const char kSympHeader[] =
+#include "hamk_symp_src.inc"
+    ;
 
 // ---------------------------------------------------------------------------
 // specialisation
@@ -92,7 +95,7 @@ static std::string cache_dir() {
 
 struct CacheKey { std::string path; unsigned char sha[32]; };
 
-static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts, bool cache_on) {
+static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts, bool cache_on, bool symp) {
   CacheKey k;
   std::memset(k.sha, 0, sizeof k.sha);
   const std::string dir = cache_on ? cache_dir() : std::string();
@@ -106,6 +109,7 @@ static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts
   feed(kDeviceHeader, sizeof kDeviceHeader);                // the headers this variant's source includes
   if (s->mapping == HAMK_MAP_WAVE) feed(kWaveHeader, sizeof kWaveHeader);
   if (s->mapping == HAMK_MAP_QUAD) feed(kQuadHeader, sizeof kQuadHeader);
+  if (symp) feed(kSympHeader, sizeof kSympHeader);          // the companion module's source includes it as well
   for (const char* o : opts) feed(o, std::strlen(o) + 1);
   feed(&major, sizeof major);
   feed(&minor, sizeof minor);
@@ -151,11 +155,11 @@ static void cache_store(const CacheKey& k, const std::vector<char>& code) {   //
   if (!out || std::rename(tmp.c_str(), k.path.c_str()) != 0) std::remove(tmp.c_str());
 }
 
-int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code) {
+int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, bool symp) {
   hiprtcProgram prog = nullptr;
-  const char* hdr_src[] = {kDeviceHeader, kWaveHeader, kQuadHeader};
-  const char* hdr_name[] = {"hamk_device.hpp", "hamk_wave.hpp", "hamk_quad.hpp"};
-  hiprtcResult r = hiprtcCreateProgram(&prog, s->source.c_str(), "hamk_system.hip", 3, hdr_src, hdr_name);
+  const char* hdr_src[] = {kDeviceHeader, kWaveHeader, kQuadHeader, kSympHeader};
+  const char* hdr_name[] = {"hamk_device.hpp", "hamk_wave.hpp", "hamk_quad.hpp", "hamk_symp.hpp"};
+  hiprtcResult r = hiprtcCreateProgram(&prog, s->source.c_str(), "hamk_system.hip", symp ? 4 : 3, hdr_src, hdr_name);
   if (r != HIPRTC_SUCCESS) return fail(HAMK_ERR_COMPILE, std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r));
   std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast",
                                    "-fno-honor-nans", "-fno-signed-zeros"};
@@ -189,7 +193,7 @@ int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<
     }
     for (auto& t : extra_tok) opts.push_back(t.c_str());
   }
-  const CacheKey ckey = cache_key(s, opts, cache_on);
+  const CacheKey ckey = cache_key(s, opts, cache_on, symp);
   if (!ckey.path.empty() && cache_load(ckey, code)) {
     s->build_log = "cache hit: " + ckey.path;
     hiprtcDestroyProgram(&prog);
@@ -285,6 +289,11 @@ int vgpr_spill_count(const std::vector<char>& elf, const char* kernel) {
   return metadata_count(elf, kernel, k, sizeof k - 1);
 }
 
+static int vgpr_count(const std::vector<char>& elf, const char* kernel) {      // the registers a kernel is allocated
+  static const char k[] = "\xab.vgpr_count";
+  return metadata_count(elf, kernel, k, sizeof k - 1);
+}
+
 static void describe_build(Variant* s);
 
 // Build the code object(s) of s->source.  Kernels that spill SGPRs under the default options are
@@ -334,6 +343,37 @@ static void describe_build(Variant* s) {
 
 size_t chosen_kernel_bytes(const Variant* s, int k) {
   return kernel_code_bytes(s->use2[k] ? s->code2 : s->code, kKernelNames[k]);
+}
+
+// ---- the symplectic stepper's companion module (hamk_symp.hpp) ---------------------------------------------------------
+// A per-system module holds exactly the nine kernels of HAMK_INSTANTIATE (tests/test_abi.py counts its function symbols and
+// the rows of build_info), and its cache key covers the whole text of hamk_device.hpp: a tenth kernel there would move every
+// existing module.  So hamk_symp_steps_k lives in a module of its own: the lane variant's generated source -- the system's
+// struct and #defines as they are, generate_source is not called again -- with its final HAMK_INSTANTIATE(HamkSys) replaced
+// by the include of hamk_symp.hpp and HAMK_INSTANTIATE_SYMP(HamkSys).  One build with the lane module's option list, through
+// the same on-disk cache; the per-kernel choice between two builds (build_code) is not made here -- DESIGN.md section 11
+// lists what the build without MachineLICM would spill.
+int build_symp(Variant* v, bool cache_on) {
+  if (!v->symp_code.empty()) return HAMK_OK;
+  static const char kTail[] = "HAMK_INSTANTIATE(HamkSys)";
+  const size_t at = v->source.rfind(kTail);
+  if (v->mapping != HAMK_MAP_LANE || at == std::string::npos) return fail(HAMK_ERR_UNSUPPORTED, "the symplectic stepper needs the one-trajectory-per-lane module");
+  Variant t;
+  t.mapping = v->mapping;
+  t.desc = v->desc;
+  t.source = v->source.substr(0, at) + "#include \"hamk_symp.hpp\"\nHAMK_INSTANTIATE_SYMP(HamkSys)" + v->source.substr(at + sizeof kTail - 1);
+  std::vector<char> code;
+  TRY0(compile_module(&t, cache_on, false, code, true));
+  static const char kName[] = "hamk_symp_steps_k";
+  char line[160];
+  // functions: the function symbols of the code object -- 1 = every device function was inlined into the one kernel
+  std::snprintf(line, sizeof line, "%s build=default bytes=%zu sgpr_spills=%d vgpr_spills=%d vgprs=%d functions=%zu\n", kName,
+                kernel_code_bytes(code, kName), sgpr_spill_count(code, kName), vgpr_spill_count(code, kName), vgpr_count(code, kName),
+                kernel_code_bytes(code, nullptr));
+  v->symp_source.swap(t.source);
+  v->symp_info = line;
+  v->symp_code.swap(code);
+  return HAMK_OK;
 }
 
 

@@ -682,8 +682,11 @@ static int post_build_checks(hamk_system* s, Variant* v) {
   return HAMK_OK;
 }
 
-int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out) {
-  const int mapping = choose_mapping(s, B, kernel);
+static int variant_of(hamk_system* s, int mapping, int64_t B, int kernel, Variant** out);
+int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out) { return variant_of(s, choose_mapping(s, B, kernel), B, kernel, out); }
+int lane_variant(hamk_system* s, Variant** out) { return variant_of(s, HAMK_MAP_LANE, INT64_MAX, K_HAMEQS, out); }
+
+static int variant_of(hamk_system* s, const int mapping, int64_t B, int kernel, Variant** out) {
   if (s->var[mapping]) { *out = s->var[mapping]; return HAMK_OK; }
   Variant* v = new Variant();
   v->mapping = mapping;

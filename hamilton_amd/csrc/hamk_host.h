@@ -106,6 +106,11 @@ struct Variant {
   int self_check_rebuilds = 0;
   bool forced_rk4_body = false, forced_rkf_body = false;
   bool has[K__COUNT] = {};     // the kernels this module provides (the quad module: four of the eight)
+  // the lane variant's COMPANION module (hamk_symp.hpp: hamk_symp_steps_k), built the first time hamk_symplectic_* asks for it;
+  // its own source, code object and one-line description -- no part of `source`, `code`, `build_info` or the kernel counts above
+  std::string symp_source;
+  std::vector<char> symp_code;
+  std::string symp_info;
 };
 constexpr int kMaxMap = 4;     // HAMK_MAP_* ids are 1..3
 
@@ -116,9 +121,12 @@ struct DevModule {
   hipFunction_t fn[K__COUNT] = {};
   bool self_checked = false;
   int code_generation = -1;     // Variant::generation the loaded modules were built from
+  hipModule_t symp_module = nullptr;      // the companion module (Variant::symp_code), loaded on first use
+  hipFunction_t symp_fn = nullptr;
   void unload() {
     if (module) { hipModuleUnload(module); module = nullptr; }
     if (module2) { hipModuleUnload(module2); module2 = nullptr; }
+    if (symp_module) { hipModuleUnload(symp_module); symp_module = nullptr; symp_fn = nullptr; }
   }
 };
 
@@ -195,7 +203,8 @@ struct hamk_system {
 namespace hamk_host {
 
 // ---- hamk_build.cpp ---------------------------------------------------------------------------------------------------
-int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code);
+int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, bool symp = false);
+int build_symp(Variant* v, bool cache_on);                 // the lane variant's companion module (hamk_symp.hpp), once
 int build_code(Variant* s, bool cache_on, int force);      // force: 0 default build only, 1 without MachineLICM only, -1 per kernel
 size_t kernel_code_bytes(const std::vector<char>& elf, const char* name);
 size_t chosen_kernel_bytes(const Variant* s, int k);
@@ -208,6 +217,7 @@ std::string check_options(const hamk_options& o, int n);
 std::string check_options(const hamk_options& o, const SystemDesc& base);      // what depends on the system: the dense quad path's capacity
 int build_force(const hamk_system* s);
 int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out);
+int lane_variant(hamk_system* s, Variant** out);            // the one-trajectory-per-lane specialisation, whatever B (n <= 16)
 int current_device_state(hamk_system* s);
 int bind_device(hamk_system* s, int64_t B, int kernel);
 int launch(hamk_system* s, KernelId k, int64_t B, void** args);

@@ -442,6 +442,17 @@ inline Phase rk4Steps(double dt, int nsteps, System& s, const Phase& ph) {
   check(hamk_rk4_steps(s.handle(), ph.B, out.positions.data(), out.momenta.data(), dt, nsteps, s.last_status.data(), HAMK_MEM_HOST));
   return out;
 }
+// symplectic fixed-step stepping (hamk_symplectic_steps; no reference counterpart): the implicit midpoint rule (order 2) or its
+// three-substep symmetric composition (order 4), `iters` fixed-point iterations per substep (0: the library's 8); n <= 16.
+// residual (optional): per trajectory the largest last-iteration update -- too large: `iters` was too small for this dt
+inline Phase symplecticSteps(double dt, int nsteps, System& s, const Phase& ph, int order = 2, int iters = 0, std::vector<double>* residual = nullptr) {
+  Phase out = ph;
+  s.last_status.assign((size_t)ph.B, 0);
+  if (residual) residual->assign((size_t)ph.B, 0.0);
+  check(hamk_symplectic_steps(s.handle(), ph.B, out.positions.data(), out.momenta.data(), dt, nsteps, order, iters,
+                              residual ? residual->data() : nullptr, s.last_status.data(), HAMK_MEM_HOST));
+  return out;
+}
 
 // ---------------------------------------------------------------------------------------
 // Ensembles resident in HBM (no reference counterpart: the reference holds one trajectory on the
@@ -513,6 +524,10 @@ inline DevicePhase samplePhaseDevice(const System& s, const Box& box, int64_t fi
 inline void setEnsembleSize(System& s, int64_t B_total) { check(hamk_system_set_ensemble_size(s.handle(), B_total)); }
 inline void rk4Steps(double dt, int nsteps, System& s, DevicePhase& d) {      // in place, asynchronous
   check(hamk_rk4_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, d.status.as<int32_t>(), HAMK_MEM_DEVICE));
+}
+inline void symplecticSteps(double dt, int nsteps, System& s, DevicePhase& d, int order = 2, int iters = 0) {      // in place, asynchronous
+  check(hamk_symplectic_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, order, iters, nullptr,
+                              d.status.as<int32_t>(), HAMK_MEM_DEVICE));
 }
 inline void stepHam(double r, System& s, DevicePhase& d) {                     // :390-402, in place, asynchronous
   check(hamk_step_ham_batch(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), r, d.status.as<int32_t>(), nullptr, HAMK_MEM_DEVICE));

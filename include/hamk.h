@@ -22,6 +22,7 @@
  *   odeSolveV's GSL binding (:445, hmatrix-gsl)         hamk_system_set_gsl_api (gsl_odeiv2 driver | old gsl_odeiv)
  *   (no counterpart; named by BASELINE.json north_star) hamk_rk4_steps        (classic fixed-step RK4)
  *   (no counterpart)            hamk_rk4_steps_checked, hamk_checkpoint_*
+ *   (no counterpart; a structure-preserving fixed step) hamk_symplectic_steps (implicit midpoint, order 2 / 4)
  *
  * The reference evaluates ONE trajectory per call on the CPU through `ad`
  * (AD), hmatrix (LAPACK/BLAS) and hmatrix-gsl (GSL odeiv).  This library
@@ -336,6 +337,29 @@ int hamk_rk4_steps(hamk_system* s, int64_t B, double* q, double* p,
  * (Hamilton.hs:321,381).  drift_tol <= 0 disables the check (= hamk_rk4_steps).               */
 int hamk_rk4_steps_checked(hamk_system* s, int64_t B, double* q, double* p,
                            double dt, int32_t nsteps, double drift_tol, int32_t* status, int32_t mem);
+
+/* Symplectic fixed-step stepping, IN PLACE on q,p: nsteps steps of dt by the implicit midpoint rule (order = 2) or its
+ * three-substep symmetric composition (order = 4); every substep takes `iters` fixed-point iterations (1..64;
+ * HAMK_AUTO = 8) -- a fixed count: cost and bits do not depend on convergence.  residual[B] (optional) receives the
+ * largest last-iteration update seen; status may be NULL.  One trajectory per lane: n <= 16; HAMK_ERR_UNSUPPORTED
+ * for n > 16 or a handle whose options state HAMK_MAP_QUAD / HAMK_MAP_WAVE.  No reference counterpart.
+ *   One substep of size h from y = [q; p]: z = y; `iters` times z <- y + (h/2) hamEqs(z); then y <- 2 z - y.  order = 4 takes
+ *   substeps g1 dt, g2 dt, g1 dt with g1 = 1 / (2 - 2^(1/3)), g2 = 1 - 2 g1.  dt < 0 steps back (the method is time-reversible).
+ *   residual = max over steps, substeps and components j of |z_j(last) - z_j(last but one)| / max(1, |y_j|): how a caller
+ *   learns that `iters` was too small for its dt; no status bit says so.  status: HAMK_ST_SINGULAR from any right-hand side,
+ *   HAMK_ST_NONFINITE where the final state is not finite.
+ *   Mapping: a handle with mapping = HAMK_AUTO ALWAYS runs this stepper on its one-trajectory-per-lane module, whatever B is
+ *   (for RK4, AUTO may pick HAMK_MAP_QUAD for small ensembles of mid-size systems; that rule does not apply here).
+ *   HAMK_MEM_DEVICE: asynchronous on the handle's stream; HAMK_MEM_HOST: staged, returns with the results in place.
+ *   B == 0 or nsteps == 0: HAMK_OK, nothing launched -- and nothing written: q, p, residual and status are left as they are
+ *   (a caller that reads residual / status after such a call clears them first).  The kernel lives in a companion module of the lane module, built the
+ *   first time one of these three entry points asks for it; the first-use self-check does not cover it.                  */
+int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps,
+                          int32_t order, int32_t iters, double* residual, int32_t* status, int32_t mem);
+/* Source / one build_info-format line (kernel, bytes, spilled SGPRs and VGPRs) of the companion module; builds it if
+ * needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported for this handle.               */
+const char* hamk_symplectic_source(hamk_system* s);
+const char* hamk_symplectic_build_info(hamk_system* s);
 
 /* stepHam dt: adaptive RKF45 with GSL's standard controller from 0 to dt,
  * h0 = dt/100, eps_abs = eps_rel = 1.49012e-08, IN PLACE.  Hamilton.hs:390-402,

@@ -87,6 +87,10 @@ def jobs():
         out.append((n, {}, False))
     out.append(("chain12", {"HAMK_QUAD": "1"}, False))
     out.append(("sampler", {}, False))
+    # the symplectic stepper's companion module (hamk_symp.hpp) of the systems tests/test_gpu_symplectic.py steps
+    for n in ("pendulum", "doublePendulum", "opcodeZoo", "room", "twoBody", "chain8", "chain16", "doublePendulum~mixed"):
+        out.append((f"symp_{n}", {}, False))
+    out.append(("symp_doublePendulum", {"HAMK_K_SYMBOLIC": "0"}, False))
     return rect + out
 
 
@@ -121,6 +125,9 @@ def build(job):
             import rect_family
             key, ask = name[5:].split("@")
             return name, env, api.system_from_spec(rect_family.spec(key), rect_family.options(None if ask == "auto" else ask)).code_size
+        elif name.startswith("symp_"):
+            s = api.system_from_spec(examples.get(name[5:]))
+            return name, env, s.symplectic_build_info.strip()
         elif name.startswith("rewrite_"):
             import rewrite_family
             key, variant = name[8:].split("@")
