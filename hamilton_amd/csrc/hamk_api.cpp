@@ -6,7 +6,6 @@
 // Haskell closures re-entering `ad` on every call; here it is an opaque handle
 // owning one compiled code object whose kernels evaluate the whole ensemble.
 #include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
 
 #include <algorithm>
 #include <cmath>
@@ -14,8 +13,6 @@
 #include <initializer_list>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -40,6 +37,20 @@ const char* const kKernelNames[K__COUNT] = {"hamk_rk4_steps_k", "hamk_hameqs_k",
 
 // ---- host-pointer staging -----------------------------------------------------
 namespace {
+// slot-th grow-only device staging block of the handle on the current device, at least `bytes` long
+int stage_slot(hamk_system* s, size_t slot, size_t bytes, void** dev) {
+  DevState* d = s->cur;
+  while (slot >= d->stage_buf.size()) { d->stage_buf.push_back(nullptr); d->stage_cap.push_back(0); }
+  if (d->stage_cap[slot] < bytes) {
+    HIP_TRY(hipStreamSynchronize(d->stream));                  // nobody may still be using the old block
+    if (d->stage_buf[slot]) hipFree(d->stage_buf[slot]);
+    d->stage_buf[slot] = nullptr; d->stage_cap[slot] = 0;
+    HIP_TRY(hipMalloc(&d->stage_buf[slot], bytes));
+    d->stage_cap[slot] = bytes;
+  }
+  *dev = d->stage_buf[slot];
+  return HAMK_OK;
+}
 struct Staged {
   void* dev = nullptr;
   void* host = nullptr;
@@ -84,16 +95,7 @@ class Stager {
       *dev = b.dev;
       return HAMK_OK;
     }
-    const size_t slot = nstaged_++;
-    if (slot >= s_->cur->stage_buf.size()) { s_->cur->stage_buf.push_back(nullptr); s_->cur->stage_cap.push_back(0); }
-    if (s_->cur->stage_cap[slot] < bytes) {
-      HIP_TRY(hipStreamSynchronize(s_->cur->stream));          // nobody may still be using the old block
-      if (s_->cur->stage_buf[slot]) hipFree(s_->cur->stage_buf[slot]);
-      s_->cur->stage_buf[slot] = nullptr; s_->cur->stage_cap[slot] = 0;
-      HIP_TRY(hipMalloc(&s_->cur->stage_buf[slot], bytes));
-      s_->cur->stage_cap[slot] = bytes;
-    }
-    b.dev = s_->cur->stage_buf[slot];
+    TRY(stage_slot(s_, nstaged_++, bytes, &b.dev));
     bufs_.push_back(b);
     if (copy_in) HIP_TRY(hipMemcpyAsync(b.dev, p, bytes, hipMemcpyHostToDevice, s_->cur->stream));
     *dev = b.dev;
@@ -307,7 +309,7 @@ int hamk_system_create_ex(int32_t m, int32_t n, const double* inertia, const ham
     if (const char* e = test_env("HAMK_MAX_SUBSTEPS")) { const long k = std::atol(e); if (k > 0 && k < (1L << 24)) s->max_substeps = (int)k; }
   // the specialisation a large ensemble uses is built now: a tape the kernels cannot be specialised for fails here
   Variant* v = nullptr;
-  const int rc = variant_for(s, INT64_MAX, K_RK4, &v);
+  const int rc = variant_for(s, INT64_MAX, &v);
   if (rc != HAMK_OK) { hamk_system_destroy(s); return rc; }
   s->info = v;
   *out = s;
@@ -332,7 +334,7 @@ int hamk_system_dims(const hamk_system* s, int32_t* m, int32_t* n) {
 int hamk_system_get_options(hamk_system* s, int64_t B, hamk_options* r) {
   if (!s || !r) return fail(HAMK_ERR_INVALID, "null system handle / options");
   Variant* v = nullptr;
-  TRY(variant_for(s, B < 0 ? INT64_MAX : B, K_RK4, &v));
+  TRY(variant_for(s, B < 0 ? INT64_MAX : B, &v));
   hamk_options_init(r);
   const SystemDesc& d = v->desc;
   r->mapping = v->mapping;
@@ -359,7 +361,7 @@ int hamk_system_get_options(hamk_system* s, int64_t B, hamk_options* r) {
 int hamk_system_describe_batch(hamk_system* s, int64_t B) {
   if (!s) return fail(HAMK_ERR_INVALID, "null system handle");
   Variant* v = nullptr;
-  TRY(variant_for(s, B < 0 ? INT64_MAX : B, K_RK4, &v));
+  TRY(variant_for(s, B < 0 ? INT64_MAX : B, &v));
   s->info = v;
   return HAMK_OK;
 }
@@ -416,14 +418,12 @@ int hamk_coords_batch(hamk_system* s, int64_t B, const double* q, double* x, int
   TRY(check_call(s, B, mem));
   if (!q || !x) return fail(HAMK_ERR_INVALID, "null q / x");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_COORDS));
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const double* dq; double* dx;
   TRY(st.in(q, (size_t)s->base.n * B, (double**)&dq));
   TRY(st.out(x, (size_t)s->base.m * B, &dx));
-  long long b = B;
-  void* args[] = {&dq, &dx, &b};
-  TRY(launch(s, K_COORDS, B, args));
+  TRY(launch_coords(s, B, dq, dx));
   return st.finish();
 }
 
@@ -431,16 +431,14 @@ int hamk_to_phase_batch(hamk_system* s, int64_t B, const double* q, const double
   TRY(check_call(s, B, mem));
   if (!q || !qd || !p) return fail(HAMK_ERR_INVALID, "null q / qd / p");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_TO_PHASE));
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   const double *dq, *dqd; double* dp;
   TRY(st.in(q, cnt, (double**)&dq));
   TRY(st.in(qd, cnt, (double**)&dqd));
   TRY(st.out(p, cnt, &dp));
-  long long b = B;
-  void* args[] = {&dq, &dqd, &dp, &b};
-  TRY(launch(s, K_TO_PHASE, B, args));
+  TRY(launch_to_phase(s, B, dq, dqd, dp));
   return st.finish();
 }
 
@@ -449,7 +447,7 @@ int hamk_from_phase_batch(hamk_system* s, int64_t B, const double* q, const doub
   TRY(check_call(s, B, mem));
   if (!q || !p || !qd) return fail(HAMK_ERR_INVALID, "null q / p / qd");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_FROM_PHASE));
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   const double *dq, *dp; double* dqd; int32_t* dst;
@@ -457,9 +455,7 @@ int hamk_from_phase_batch(hamk_system* s, int64_t B, const double* q, const doub
   TRY(st.in(p, cnt, (double**)&dp));
   TRY(st.out(qd, cnt, &dqd));
   TRY(st.out(status, (size_t)B, &dst));
-  long long b = B;
-  void* args[] = {&dq, &dp, &dqd, &b, &dst};
-  TRY(launch(s, K_FROM_PHASE, B, args));
+  TRY(launch_from_phase(s, B, dq, dp, dqd, dst));
   return st.finish();
 }
 
@@ -469,7 +465,7 @@ int hamk_observe_batch(hamk_system* s, int64_t B, const double* q, const double*
   if (!q) return fail(HAMK_ERR_INVALID, "null q");
   if (!p && (ke || h)) return fail(HAMK_ERR_INVALID, "ke / h need momenta p");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_OBSERVE));
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   const double *dq, *dp; double *dke, *dpe, *dh; int32_t* dst;
@@ -479,9 +475,7 @@ int hamk_observe_batch(hamk_system* s, int64_t B, const double* q, const double*
   TRY(st.out(pe, (size_t)B, &dpe));
   TRY(st.out(h, (size_t)B, &dh));
   TRY(st.out(status, (size_t)B, &dst));
-  long long b = B;
-  void* args[] = {&dq, &dp, &dke, &dpe, &dh, &b, &dst};
-  TRY(launch(s, K_OBSERVE, B, args));
+  TRY(launch_observe(s, B, dq, dp, dke, dpe, dh, dst));
   return st.finish();
 }
 
@@ -490,7 +484,7 @@ int hamk_observe_config_batch(hamk_system* s, int64_t B, const double* q, const 
   TRY(check_call(s, B, mem));
   if (!q || !qd) return fail(HAMK_ERR_INVALID, "null q / qd");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_OBSERVE_CFG));
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   const double *dq, *dqd; double *dke, *dlag;
@@ -498,9 +492,7 @@ int hamk_observe_config_batch(hamk_system* s, int64_t B, const double* q, const 
   TRY(st.in(qd, cnt, (double**)&dqd));
   TRY(st.out(ke, (size_t)B, &dke));
   TRY(st.out(lag, (size_t)B, &dlag));
-  long long b = B;
-  void* args[] = {&dq, &dqd, &dke, &dlag, &b};
-  TRY(launch(s, K_OBSERVE_CFG, B, args));
+  TRY(launch_observe_config(s, B, dq, dqd, dke, dlag));
   return st.finish();
 }
 
@@ -509,7 +501,7 @@ int hamk_hameqs_batch(hamk_system* s, int64_t B, const double* q, const double* 
   TRY(check_call(s, B, mem));
   if (!q || !p || !dq || !dp) return fail(HAMK_ERR_INVALID, "null q / p / dq / dp");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_HAMEQS));
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   const double *xq, *xp; double *xdq, *xdp; int32_t* dst;
@@ -518,13 +510,9 @@ int hamk_hameqs_batch(hamk_system* s, int64_t B, const double* q, const double* 
   TRY(st.out(dq, cnt, &xdq));
   TRY(st.out(dp, cnt, &xdp));
   TRY(st.out(status, (size_t)B, &dst));
-  long long b = B;
-  void* args[] = {&xq, &xp, &xdq, &xdp, &b, &dst};
-  TRY(launch(s, K_HAMEQS, B, args));
+  TRY(launch_hameqs(s, B, xq, xp, xdq, xdp, dst));
   return st.finish();
 }
-
-namespace { struct HamkBoxes { double q_lo[64], q_hi[64], qd_lo[64], qd_hi[64]; }; }     // = hamk_sample.hpp
 
 // The sampler is the one JIT product that every other check of the library takes on trust (shard invariance, bench parity and the
 // CPU tests' numpy sampler all rest on "index -> bits" being what hamk_sample.hpp says): on its first use per device, eight
@@ -552,18 +540,12 @@ static int sample_self_check(DevState* d) {
   std::memset(&bx, 0, sizeof bx);
   bx.q_lo[0] = -1.25; bx.q_hi[0] = 2.5; bx.q_lo[1] = 0.5; bx.q_hi[1] = 0.75;
   bx.qd_lo[0] = -3.0; bx.qd_hi[0] = 3.0; bx.qd_lo[1] = 1e-3; bx.qd_hi[1] = 1e3;
-  double* dev = nullptr;
-  HIP_TRY(hipMalloc((void**)&dev, 2 * n * B * sizeof(double)));
-  double *xq = dev, *xqd = dev + n * B;
-  long long b = B, f0 = first;
-  unsigned long long sd = seed;
-  int nn = n;
-  void* args[] = {&xq, &xqd, &b, &f0, &sd, &nn, &bx};
+  DevBuf<double> dev;
+  TRY(dev.alloc(2 * n * B));
   double got[2 * n * B];
-  hipError_t e = hipModuleLaunchKernel(d->sample_fn, 1, 1, 1, 256, 1, 1, 0, d->stream, args, nullptr);
-  if (e == hipSuccess) e = hipMemcpyAsync(got, dev, sizeof got, hipMemcpyDeviceToHost, d->stream);
+  TRY(launch_sample(d, B, dev.p, dev.p + n * B, first, seed, n, bx));
+  hipError_t e = hipMemcpyAsync(got, dev.p, sizeof got, hipMemcpyDeviceToHost, d->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-  hipFree(dev);
   if (e != hipSuccess) return fail(HAMK_ERR_HIP, std::string("sampler self-check: ") + hipGetErrorString(e));
   if (const char* f = test_env("HAMK_SELFCHECK_FAULT")) if (std::strstr(f, "sample")) got[3] = std::nextafter(got[3], 4.0);      // test hook: one bit off
   for (int j = 0; j < n; ++j)
@@ -605,13 +587,7 @@ int hamk_sample_batch(hamk_system* s, int64_t B, int64_t first_index, uint64_t s
   double *xq, *xqd;
   TRY(st.out(q, cnt, &xq));
   TRY(st.out(qd, cnt, &xqd));
-  long long b = B, first = first_index;
-  unsigned long long sd = seed;
-  int nn = n;
-  void* args[] = {&xq, &xqd, &b, &first, &sd, &nn, &bx};
-  const int64_t grid = (B + 255) / 256;
-  if (grid > 0x7fffffffLL) return fail(HAMK_ERR_INVALID, "ensemble too large for one launch");
-  HIP_TRY(hipModuleLaunchKernel(d->sample_fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, d->stream, args, nullptr));
+  TRY(launch_sample(d, B, xq, xqd, first_index, seed, n, bx));
   return st.finish();
 }
 
@@ -638,20 +614,6 @@ static int64_t piece_size() {
 static bool host_pieces_on() {
   static const bool off = [] { const char* e = test_env("HAMK_HOST_PIECES"); return e && e[0] == '0'; }();
   return !off;
-}
-
-static int stage_slot(hamk_system* s, size_t slot, size_t bytes, void** dev) {
-  DevState* d = s->cur;
-  while (slot >= d->stage_buf.size()) { d->stage_buf.push_back(nullptr); d->stage_cap.push_back(0); }
-  if (d->stage_cap[slot] < bytes) {
-    HIP_TRY(hipStreamSynchronize(d->stream));                  // nobody may still be using the old block
-    if (d->stage_buf[slot]) hipFree(d->stage_buf[slot]);
-    d->stage_buf[slot] = nullptr; d->stage_cap[slot] = 0;
-    HIP_TRY(hipMalloc(&d->stage_buf[slot], bytes));
-    d->stage_cap[slot] = bytes;
-  }
-  *dev = d->stage_buf[slot];
-  return HAMK_OK;
 }
 
 static int rk4_steps_host_pieces(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, double drift_tol,
@@ -690,13 +652,8 @@ static int rk4_steps_host_pieces(hamk_system* s, int64_t B, double* q, double* p
   };
   auto step = [&](int c) -> int {
     const int64_t at = (int64_t)c * kPiece;
-    double *xq = dq + (size_t)n * at, *xp = dp + (size_t)n * at;
-    int32_t* xs = dst ? dst + at : nullptr;
-    long long b = count(c);
-    int ns = nsteps;
-    void* args[] = {&xq, &xp, &b, &dt, &ns, &drift_tol, &xs};
     HIP_TRY(hipStreamWaitEvent(S, d->piece_events[2 * c], 0));
-    TRY(launch(s, K_RK4, b, args));
+    TRY(launch_rk4(s, count(c), dq + (size_t)n * at, dp + (size_t)n * at, dt, nsteps, drift_tol, dst ? dst + at : nullptr));
     HIP_TRY(hipEventRecord(d->piece_events[2 * c + 1], S));
     return HAMK_OK;
   };
@@ -733,7 +690,7 @@ int hamk_rk4_steps_checked(hamk_system* s, int64_t B, double* q, double* p, doub
   if (nsteps < 0) return fail(HAMK_ERR_INVALID, "negative nsteps");
   if (drift_tol != drift_tol) return fail(HAMK_ERR_INVALID, "drift_tol is NaN");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_RK4));
+  TRY(bind_device(s, B));
   if (mem == HAMK_MEM_HOST && B >= 2 * piece_size() && (int64_t)nsteps * s->base.n >= 64 && host_pieces_on()) return rk4_steps_host_pieces(s, B, q, p, dt, nsteps, drift_tol, status);
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
@@ -741,10 +698,7 @@ int hamk_rk4_steps_checked(hamk_system* s, int64_t B, double* q, double* p, doub
   TRY(st.inout(q, cnt, &xq));
   TRY(st.inout(p, cnt, &xp));
   TRY(st.out(status, (size_t)B, &dst));
-  long long b = B;
-  int ns = nsteps;
-  void* args[] = {&xq, &xp, &b, &dt, &ns, &drift_tol, &dst};
-  TRY(launch(s, K_RK4, B, args));
+  TRY(launch_rk4(s, B, xq, xp, dt, nsteps, drift_tol, dst));
   return st.finish();
 }
 
@@ -798,10 +752,7 @@ int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, doubl
   }
   // order 4: substeps g1 dt, g2 dt, g1 dt with g1 = 1 / (2 - 2^(1/3)), g2 = 1 - 2 g1 (negative: the middle substep goes back)
   const double g1 = 1.0 / (2.0 - std::pow(2.0, 1.0 / 3.0)), g2 = 1.0 - 2.0 * g1;
-  double ha = order == 4 ? g1 * dt : dt, hb = order == 4 ? g2 * dt : 0.0;
-  int nsub = order == 4 ? 3 : 1, ns = nsteps, it = iters == HAMK_AUTO ? 8 : iters;
-  const int64_t grid = (B + 255) / 256;
-  if (grid > 0x7fffffffLL) return fail(HAMK_ERR_INVALID, "ensemble too large for one launch");
+  const double ha = order == 4 ? g1 * dt : dt, hb = order == 4 ? g2 * dt : 0.0;
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   double *xq, *xp, *xr; int32_t* dst;
@@ -809,9 +760,7 @@ int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, doubl
   TRY(st.inout(p, cnt, &xp));
   TRY(st.out(residual, (size_t)B, &xr));
   TRY(st.out(status, (size_t)B, &dst));
-  long long b = B;
-  void* args[] = {&xq, &xp, &b, &ns, &nsub, &ha, &hb, &it, &xr, &dst};
-  HIP_TRY(hipModuleLaunchKernel(m.symp_fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, s->cur->stream, args, nullptr));
+  TRY(launch_symp(s, B, xq, xp, nsteps, order == 4 ? 3 : 1, ha, hb, iters == HAMK_AUTO ? 8 : iters, xr, dst));
   return st.finish();
 }
 
@@ -829,7 +778,6 @@ static int upload_times(hamk_system* s, int32_t nt, const double* ts) {
   return HAMK_OK;
 }
 
-static const double kRefEps = 1.49012e-08;   // Hamilton.hs:448
 int hamk_evolve_ham_batch(hamk_system* s, int64_t B, const double* q0, const double* p0, int32_t nt, const double* ts,
                           double* qout, double* pout, double h0, double eps_abs, double eps_rel, int32_t* status,
                           int32_t* nsub, int32_t mem) {
@@ -837,7 +785,7 @@ int hamk_evolve_ham_batch(hamk_system* s, int64_t B, const double* q0, const dou
   if (!q0 || !p0 || !qout || !pout || !ts) return fail(HAMK_ERR_INVALID, "null q0 / p0 / ts / qout / pout");
   if (nt < 2) return fail(HAMK_ERR_INVALID, "evolveHam needs at least two times (2 <= s, Hamilton.hs:435)");
   if (B == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_RKF45));
+  TRY(bind_device(s, B));
   if (!(h0 > 0.0)) h0 = (ts[1] - ts[0]) / 100.0;          // Hamilton.hs:447
   if (!(eps_abs > 0.0)) eps_abs = kRefEps;
   if (!(eps_rel > 0.0)) eps_rel = kRefEps;
@@ -854,7 +802,6 @@ int hamk_evolve_ham_batch(hamk_system* s, int64_t B, const double* q0, const dou
   Stager st(s, mem);
   // time grid: two times travel as kernel arguments; a longer grid as a pinned side input of a
   // small host-pointer call, else through the handle's device scratch
-  double ts0 = ts[0], ts1 = ts[1];
   const double* dts = nullptr;
   if (nt > 2) {
     dts = (size_t)nt * sizeof(double) <= kPinMaxBuf ? st.side_input(ts, (size_t)nt) : nullptr;
@@ -868,11 +815,13 @@ int hamk_evolve_ham_batch(hamk_system* s, int64_t B, const double* q0, const dou
   TRY(st.out(pout, cnt * nt, &xpo));
   TRY(st.out(status, (size_t)B, &dst));
   TRY(st.out(nsub, (size_t)B, &dns));
-  long long b = B;
-  int nt_ = nt, flags = rkf_flags(0, 0, s->gsl_api), max_sub = s->max_substeps;
-  int ncalls = 1, it_every = 0;
-  void* args[] = {&xq, &xp, &xqo, &xpo, &b, &nt_, &dts, &ts0, &ts1, &h0, &eps_abs, &eps_rel, &flags, &max_sub, &dst, &dns, &ncalls, &it_every};
-  TRY(launch(s, K_RKF45, B, args));
+  RkfCall c;
+  c.q0 = xq; c.p0 = xp; c.qout = xqo; c.pout = xpo;
+  c.nt = nt; c.ts = dts; c.ts0 = ts[0]; c.ts1 = ts[1];
+  c.h0 = h0; c.eps_abs = eps_abs; c.eps_rel = eps_rel;
+  c.gsl_api = s->gsl_api; c.max_sub = s->max_substeps;
+  c.status = dst; c.nsub = dns;
+  TRY(launch_rkf45(s, B, c));
   return st.finish();
 }
 
@@ -883,9 +832,7 @@ int hamk_step_ham_iterate(hamk_system* s, int64_t B, double* q, double* p, doubl
   if (ncalls < 0 || out_every < 0) return fail(HAMK_ERR_INVALID, "negative ncalls / out_every");
   if (out_every > 0 && (!qout || !pout)) return fail(HAMK_ERR_INVALID, "out_every > 0 needs qout / pout");
   if (B == 0 || ncalls == 0) return HAMK_OK;
-  TRY(bind_device(s, B, K_RKF45));
-  double ts0 = 0.0, ts1 = dt;                               // evolveHam over (0, r), Hamilton.hs:401
-  double h0 = dt / 100.0, eps_abs = kRefEps, eps_rel = kRefEps;
+  TRY(bind_device(s, B));
   Stager st(s, mem);
   const size_t cnt = (size_t)s->base.n * B;
   const size_t rows = out_every > 0 ? (size_t)(ncalls / out_every) : 0;
@@ -895,14 +842,14 @@ int hamk_step_ham_iterate(hamk_system* s, int64_t B, double* q, double* p, doubl
   if (rows > 0) { TRY(st.out(qout, cnt * rows, &xqo)); TRY(st.out(pout, cnt * rows, &xpo)); }
   TRY(st.out(status, (size_t)B, &dst));
   TRY(st.out(nsub, (size_t)B, &dns));
-  long long b = B;
   // in place on (q, p); the kernel's qout/pout receive the frames (hamk_device.hpp rkf45_body, flags)
-  int nt_ = 2, flags = rkf_flags(1, 2, s->gsl_api), max_sub = s->max_substeps;
-  int nc = ncalls, every = rows > 0 ? out_every : 0;
-  const double* dts = nullptr;
-  const double *cq = xq, *cp = xp;
-  void* args[] = {&cq, &cp, &xqo, &xpo, &b, &nt_, &dts, &ts0, &ts1, &h0, &eps_abs, &eps_rel, &flags, &max_sub, &dst, &dns, &nc, &every};
-  TRY(launch(s, K_RKF45, B, args));
+  RkfCall c;
+  c.q0 = xq; c.p0 = xp; c.qout = xqo; c.pout = xpo;
+  c.ts1 = dt; c.h0 = dt / 100.0;                            // evolveHam over (0, r) with the reference's tolerances, Hamilton.hs:401
+  c.row0 = 1; c.inplace = 2; c.gsl_api = s->gsl_api; c.max_sub = s->max_substeps;
+  c.status = dst; c.nsub = dns;
+  c.ncalls = ncalls; c.it_every = rows > 0 ? out_every : 0;
+  TRY(launch_rkf45(s, B, c));
   return st.finish();
 }
 

@@ -363,7 +363,7 @@ int build_symp(Variant* v, bool cache_on) {
   t.desc = v->desc;
   t.source = v->source.substr(0, at) + "#include \"hamk_symp.hpp\"\nHAMK_INSTANTIATE_SYMP(HamkSys)" + v->source.substr(at + sizeof kTail - 1);
   std::vector<char> code;
-  TRY0(compile_module(&t, cache_on, false, code, true));
+  TRY(compile_module(&t, cache_on, false, code, true));
   static const char kName[] = "hamk_symp_steps_k";
   char line[160];
   // functions: the function symbols of the code object -- 1 = every device function was inlined into the one kernel
@@ -379,8 +379,6 @@ int build_symp(Variant* v, bool cache_on) {
 
 
 // ---- initial conditions on the device ----------------------------------------------------------------
-namespace { struct HamkBoxes { double q_lo[64], q_hi[64], qd_lo[64], qd_hi[64]; }; }     // = hamk_sample.hpp
-
 int sample_code(bool cache_on, const std::vector<char>** out) {     // the sampler's code object: compiled once per process
   static std::mutex mu;
   static std::vector<char> code;
@@ -389,7 +387,7 @@ int sample_code(bool cache_on, const std::vector<char>** out) {     // the sampl
     Variant v;
     v.mapping = HAMK_MAP_LANE;
     v.source = kSampleSource;
-    TRY0(compile_module(&v, cache_on, false, code));
+    TRY(compile_module(&v, cache_on, false, code));
   }
   *out = &code;
   return HAMK_OK;

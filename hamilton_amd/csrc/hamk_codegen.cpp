@@ -90,20 +90,21 @@ std::string validate_tape(const hamk_op* ops, int nops, int n_in, const int32_t*
 // kernels, M up to 64).
 // input_exprs (optional): expression to use for INPUT j instead of in[j] (composition u . f);
 // tc_name: the trig cache variable the body's sincos sites use.
-// Values of the tape being emitted that somebody outside emit_body reads by name (the tape's outputs): set by generate_source
-// before every call.  A value in it is always materialised.
-static std::vector<char> g_emit_is_output;
-// Dense maps on the four-lane kernels (SystemDesc::quad_dense): products `constant x value` that SEVERAL outputs read are not
-// materialised once but written out at every use with the constant behind an opaque copy -- a tape whose n^2 coefficients come from
-// a small table (the benchmark maps dense24 / dense32: 11 x 7 values) shares each product a sin q_j between ~n / 11 outputs, and a
-// shared value lives from its first reader to its last: hundreds of them at once, i.e. scratch (dense32: 3 666 spilled registers, the
-// library went back to the wave kernels).  Unshared, such a tape compiles like one with distinct coefficients.
-static bool g_emit_unshare_scales = false;
-static void mark_outputs(size_t nops, const int32_t* outs, int n_out) {
-  g_emit_is_output.assign(nops, 0);
-  for (int k = 0; k < n_out; ++k) g_emit_is_output[(size_t)outs[k]] = 1;
-}
-static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const char* pfx,
+// EmitCtx: what generate_source knows about the tape being emitted and emit_body cannot see from the operations alone.
+//   is_output: the values somebody outside emit_body reads by name (the tape's outputs); such a value is always materialised.
+//   unshare_scales: dense maps on the four-lane kernels (SystemDesc::quad_dense): products `constant x value` that SEVERAL outputs read
+//   are not materialised once but written out at every use with the constant behind an opaque copy -- a tape whose n^2 coefficients come
+//   from a small table (the benchmark maps dense24 / dense32: 11 x 7 values) shares each product a sin q_j between ~n / 11 outputs, and
+//   a shared value lives from its first reader to its last: hundreds of them at once, i.e. scratch (dense32: 3 666 spilled registers,
+//   the library went back to the wave kernels).  Unshared, such a tape compiles like one with distinct coefficients.
+struct EmitCtx {
+  std::vector<char> is_output;
+  bool unshare_scales = false;
+  EmitCtx(size_t nops, const int32_t* outs, int n_out, bool unshare) : is_output(nops, 0), unshare_scales(unshare) {
+    for (int k = 0; k < n_out; ++k) is_output[(size_t)outs[k]] = 1;
+  }
+};
+static int emit_body(const EmitCtx& cx, std::ostringstream& o, const hamk_op* ops, int nops, const char* pfx,
                      const std::vector<std::vector<int>>* sink_outs = nullptr,
                      const std::vector<std::string>* input_exprs = nullptr, const char* tc_name = "tc",
                      std::vector<int>* slot_operand = nullptr, const char* trig_mode = "TRIG",
@@ -128,7 +129,7 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
   }
   for (int i = 0; i < nops; ++i)
     if (ops[i].op == HAMK_OP_RECIP && ops[ops[i].a].op == HAMK_OP_SQRT && uses[ops[i].a] == 1 &&
-        !((size_t)ops[i].a < g_emit_is_output.size() && g_emit_is_output[(size_t)ops[i].a]) && !(sink_outs && !(*sink_outs)[ops[i].a].empty())) {
+        !cx.is_output[(size_t)ops[i].a] && !(sink_outs && !(*sink_outs)[ops[i].a].empty())) {
       fused_rsqrt[i] = 1;
       done[ops[i].a] = 2;                                   // the square root itself is never emitted
     }
@@ -201,7 +202,7 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
   // that is a reference; with the wave kernels' LDS-backed proxies it keeps 32 input jets from
   // all being live from the top of the function (the tape lists its inputs first).
   std::vector<char> inline_scale(nops, 0);
-  if (g_emit_unshare_scales) {
+  if (cx.unshare_scales) {
     std::vector<int> nuse(nops, 0);
     for (int i = 0; i < nops; ++i) {
       const hamk_op& p = ops[i];
@@ -211,7 +212,7 @@ static int emit_body(std::ostringstream& o, const hamk_op* ops, int nops, const 
     }
     for (int i = 0; i < nops; ++i)
       if (ops[i].op == HAMK_OP_MUL && nuse[i] > 1 && (ops[ops[i].a].op == HAMK_OP_CONST) != (ops[ops[i].b].op == HAMK_OP_CONST) &&
-          !((size_t)i < g_emit_is_output.size() && g_emit_is_output[(size_t)i]) && !(sink_outs && !(*sink_outs)[i].empty()))
+          !cx.is_output[(size_t)i] && !(sink_outs && !(*sink_outs)[i].empty()))
         inline_scale[i] = 1;
   }
   std::function<std::string(int)> v = [&](int i) -> std::string {
@@ -1068,17 +1069,14 @@ std::string generate_source(const SystemDesc& d) {
   // coordinate map f: generalized -> cartesian                       (_sysCoords, Hamilton.hs:220)
   o << "  template <class A, int TRIG, class TC> __device__ __forceinline__ static void coords(const A (&in)[N], A (&x)[M], TC& tc) {\n";
   std::vector<int> slot_operand;
-  auto mark_f = [&] { mark_outputs(d.f_ops.size(), d.f_outs.data(), d.m); g_emit_unshare_scales = d.mapping == HAMK_MAP_QUAD && d.quad_dense; };
-  auto mark_u = [&] { mark_outputs(d.u_ops.size(), &d.u_out, 1); g_emit_unshare_scales = false; };
-  mark_f();
-  const int ntrig_f = emit_body(o, d.f_ops.data(), (int)d.f_ops.size(), "f", nullptr, nullptr, "tc", &slot_operand);
+  const EmitCtx cf(d.f_ops.size(), d.f_outs.data(), d.m, d.mapping == HAMK_MAP_QUAD && d.quad_dense), cu(d.u_ops.size(), &d.u_out, 1, false);
+  const int ntrig_f = emit_body(cf, o, d.f_ops.data(), (int)d.f_ops.size(), "f", nullptr, nullptr, "tc", &slot_operand);
   for (int k = 0; k < d.m; ++k) o << "    x[" << k << "] = hamk::lift<A>(" << value_name(d.f_ops, "f", d.f_outs[k]) << ");\n";
   o << "  }\n";
   // potential                                                         (_sysPotential, Hamilton.hs:223 / :254)
   const int nu = d.u_space == HAMK_U_CARTESIAN ? d.m : d.n;
   o << "  template <class A, int TRIG, class TC> __device__ __forceinline__ static A potential(const A (&in)[" << nu << "], TC& tc) {\n";
-  mark_u();
-  const int ntrig_u = emit_body(o, d.u_ops.data(), (int)d.u_ops.size(), "u");
+  const int ntrig_u = emit_body(cu, o, d.u_ops.data(), (int)d.u_ops.size(), "u");
   o << "    return hamk::lift<A>(" << value_name(d.u_ops, "u", d.u_out) << ");\n";
   o << "  }\n";
   // the same potential evaluated right after f at the same generalized coordinates: sincos sites of
@@ -1098,8 +1096,7 @@ std::string generate_source(const SystemDesc& d) {
     o << "  template <class A, int TRIG, class TC, class TCF> __device__ __forceinline__ static A potential_after_f(const A (&in)[" << nu
       << "], TC& tc, TCF& tcf) {\n";
     if (any) {
-      mark_u();
-      emit_body(o, d.u_ops.data(), (int)d.u_ops.size(), "u", nullptr, nullptr, "tc", nullptr, "TRIG", &f_slot_of_input);
+      emit_body(cu, o, d.u_ops.data(), (int)d.u_ops.size(), "u", nullptr, nullptr, "tc", nullptr, "TRIG", &f_slot_of_input);
       o << "    return hamk::lift<A>(" << value_name(d.u_ops, "u", d.u_out) << ");\n";
     } else {
       o << "    return potential<A, TRIG>(in, tc);\n";
@@ -1111,20 +1108,17 @@ std::string generate_source(const SystemDesc& d) {
   std::vector<std::vector<int>> sink_outs(d.f_ops.size());
   for (int k = 0; k < d.m; ++k) sink_outs[d.f_outs[k]].push_back(k);
   std::vector<int> put_order;                               // output index of the SEQ-th put
-  mark_f();
-  emit_body(o, d.f_ops.data(), (int)d.f_ops.size(), "f", &sink_outs, nullptr, "tc", nullptr, "TRIG", nullptr, &put_order);
+  emit_body(cf, o, d.f_ops.data(), (int)d.f_ops.size(), "f", &sink_outs, nullptr, "tc", nullptr, "TRIG", nullptr, &put_order);
   o << "  }\n";
   // f with a sink, followed by the potential on the same SSA values (u . f when U is cartesian):
   // no array of M outputs is ever materialised
   o << "  template <class A, int TRIG, class IN, class TC, class TCU, class Sink> __device__ __forceinline__ static A coords_sink_u(const IN& in, TC& tc, TCU& tcu, Sink& sink) {\n";
-  mark_f();
-  emit_body(o, d.f_ops.data(), (int)d.f_ops.size(), "f", &sink_outs);
+  emit_body(cf, o, d.f_ops.data(), (int)d.f_ops.size(), "f", &sink_outs);
   {
     std::vector<std::string> u_in;
     if (d.u_space == HAMK_U_CARTESIAN) for (int k = 0; k < d.m; ++k) u_in.push_back(value_name(d.f_ops, "f", d.f_outs[k]));
     else for (int j = 0; j < d.n; ++j) u_in.push_back("in[" + std::to_string(j) + "]");
-    mark_u();
-    emit_body(o, d.u_ops.data(), (int)d.u_ops.size(), "u", nullptr, &u_in, "tcu", nullptr, "hamk::TRIG_FULL");
+    emit_body(cu, o, d.u_ops.data(), (int)d.u_ops.size(), "u", nullptr, &u_in, "tcu", nullptr, "hamk::TRIG_FULL");
     o << "    return hamk::lift<A>(" << value_name(d.u_ops, "u", d.u_out, &u_in) << ");\n";
   }
   o << "  }\n";

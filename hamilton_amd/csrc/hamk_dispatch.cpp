@@ -1,7 +1,6 @@
 // hamk_dispatch.cpp -- options -> specialisations, device binding, launches, first-use self-check (host side of
 // libhamk.so, see hamk_host.h).
 #include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
 
 #include <algorithm>
 #include <cmath>
@@ -9,13 +8,8 @@
 #include <initializer_list>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <mutex>
 #include <string>
 #include <vector>
-
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include "hamk_host.h"
 
@@ -27,7 +21,6 @@ const char* test_env(const char* name) {
   return (on && on[0] == '1' && on[1] == 0) ? std::getenv(name) : nullptr;
 }
 
-// hamk_options::build, else HAMK_NOLICM (tests), else per kernel
 int build_force(const hamk_system* s) {                      // hamk_options::build, else HAMK_NOLICM (tests), else per kernel
   if (s->opt.build == HAMK_BUILD_DEFAULT) return 0;
   if (s->opt.build == HAMK_BUILD_NOLICM) return 1;
@@ -35,9 +28,6 @@ int build_force(const hamk_system* s) {                      // hamk_options::bu
   return -1;
 }
 
-int launch(hamk_system* s, KernelId k, int64_t B, void** args);
-// the flags argument of hamk_rkf45_k (hamk_device.hpp rkf45_body)
-int rkf_flags(int row0, int inplace, int gsl_api) { return (row0 & 1) | ((inplace & 3) << 8) | ((gsl_api & 3) << 16); }
 static int load_modules(hamk_system* s);
 
 // ---------------------------------------------------------------------------
@@ -49,7 +39,6 @@ static int load_modules(hamk_system* s);
 // module is rebuilt once with the stage-loop bodies; if that does not help, the system is refused.
 // HAMK_SELFCHECK=0 skips it.
 // ---------------------------------------------------------------------------
-static const double kRefEpsilon = 1.49012e-08;   // Hamilton.hs:448
 static thread_local std::string g_selfcheck_detail;
 static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
   g_selfcheck_detail.clear();
@@ -62,30 +51,18 @@ static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
       q[(size_t)j * B + i] = 0.31 + 0.07 * j + 0.011 * (double)i;
       p[(size_t)j * B + i] = 0.23 - 0.05 * j + 0.007 * (double)i;
     }
-  // device scratch of the check, released on every path out of this function
-  struct Scratch {
-    void* p[5] = {};
-    ~Scratch() { for (void* x : p) if (x) hipFree(x); }
-  } scratch;
-  HIP_TRY(hipMalloc(&scratch.p[0], cnt * 8)); HIP_TRY(hipMalloc(&scratch.p[1], cnt * 8));
-  HIP_TRY(hipMalloc(&scratch.p[2], cnt * 8)); HIP_TRY(hipMalloc(&scratch.p[3], cnt * 8));
-  HIP_TRY(hipMalloc(&scratch.p[4], B * 4));
-  double *d_q = (double*)scratch.p[0], *d_p = (double*)scratch.p[1], *d_dq = (double*)scratch.p[2], *d_dp = (double*)scratch.p[3];
-  int32_t* d_st = (int32_t*)scratch.p[4];
-  long long b = B;
+  DevBuf<double> d_q, d_p, d_dq, d_dp;
+  DevBuf<int32_t> d_st;
+  TRY(d_q.alloc(cnt)); TRY(d_p.alloc(cnt)); TRY(d_dq.alloc(cnt)); TRY(d_dp.alloc(cnt)); TRY(d_st.alloc((size_t)B));
   bool flagged = false;
+  auto ran = [&](const char* failed) { return hipStreamSynchronize(s->cur->stream) == hipSuccess ? HAMK_OK : fail(HAMK_ERR_HIP, failed); };
   auto rhs = [&](const std::vector<double>& y, std::vector<double>& out) -> int {   // out = hamEqs(y), y = [q; p]
-    HIP_TRY(hipMemcpy(d_q, y.data(), cnt * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_p, y.data() + cnt, cnt * 8, hipMemcpyHostToDevice));
-    const double *cq = d_q, *cp = d_p; int32_t* st = d_st;
-    void* args[] = {&cq, &cp, &d_dq, &d_dp, &b, &st};
-    int rc = launch(s, K_HAMEQS, B, args);
-    if (rc != HAMK_OK) return rc;
+    TRY(d_q.put(y.data(), cnt)); TRY(d_p.put(y.data() + cnt, cnt));
+    TRY(launch_hameqs(s, B, d_q.p, d_p.p, d_dq.p, d_dp.p, d_st.p));
     HIP_TRY(hipStreamSynchronize(s->cur->stream));
-    HIP_TRY(hipMemcpy(out.data(), d_dq, cnt * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out.data() + cnt, d_dp, cnt * 8, hipMemcpyDeviceToHost));
+    TRY(d_dq.get(out.data(), cnt)); TRY(d_dp.get(out.data() + cnt, cnt));
     std::vector<int32_t> hst((size_t)B);
-    HIP_TRY(hipMemcpy(hst.data(), d_st, (size_t)B * 4, hipMemcpyDeviceToHost));
+    TRY(d_st.get(hst.data(), (size_t)B));
     for (int32_t v : hst) if (v != 0) flagged = true;    // singular / non-finite at the test points: cannot judge
     return HAMK_OK;
   };
@@ -105,7 +82,6 @@ static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
   };
   std::vector<double> y0(2 * cnt), got(2 * cnt), ref(2 * cnt);
   std::copy(q.begin(), q.end(), y0.begin()); std::copy(p.begin(), p.end(), y0.begin() + cnt);
-  int rc = HAMK_OK;
   bool usable = true;
   // ---- RK4: one step of dt -------------------------------------------------------------------
   // dt = 1e-3 unless the right-hand side at the test points is large (a 64-link chain with these
@@ -113,33 +89,37 @@ static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
   // step is a small perturbation of the state, so dt keeps the largest increment at 0.05.
   double dt = 1e-3;
   {
-    rc = rhs(y0, k);
+    TRY(rhs(y0, k));
     double kmax = 0.0;
     for (size_t i = 0; i < 2 * cnt; ++i) if (std::isfinite(k[i]) && std::fabs(k[i]) > kmax) kmax = std::fabs(k[i]);
     if (kmax * dt > 0.05) dt = 0.05 / kmax;
   }
-  if (rc == HAMK_OK) {
+  {
     const double a[4] = {0.0, 0.5 * dt, 0.5 * dt, dt}, w[4] = {dt / 6, dt / 3, dt / 3, dt / 6};
     ref = y0;
     std::fill(k.begin(), k.end(), 0.0);
-    for (int sg = 0; sg < 4 && rc == HAMK_OK; ++sg) {
+    for (int sg = 0; sg < 4; ++sg) {
       for (size_t i = 0; i < 2 * cnt; ++i) yt[i] = y0[i] + a[sg] * k[i];
-      rc = rhs(yt, k);
+      TRY(rhs(yt, k));
       for (size_t i = 0; i < 2 * cnt; ++i) ref[i] += w[sg] * k[i];
     }
-    if (rc == HAMK_OK) {
-      hipMemcpy(d_q, q.data(), cnt * 8, hipMemcpyHostToDevice); hipMemcpy(d_p, p.data(), cnt * 8, hipMemcpyHostToDevice);
-      double ddt = dt, no_drift = 0.0; int ns = 1; int32_t* st = d_st;
-      void* args[] = {&d_q, &d_p, &b, &ddt, &ns, &no_drift, &st};
-      rc = launch(s, K_RK4, B, args);
-      if (rc == HAMK_OK && hipStreamSynchronize(s->cur->stream) != hipSuccess) rc = fail(HAMK_ERR_HIP, "self-check: RK4 kernel failed");
-      hipMemcpy(got.data(), d_q, cnt * 8, hipMemcpyDeviceToHost); hipMemcpy(got.data() + cnt, d_p, cnt * 8, hipMemcpyDeviceToHost);
-      *rk4_ok = close_enough(got, ref, &usable, "one RK4 step");
-    }
+    TRY(d_q.put(q.data(), cnt)); TRY(d_p.put(p.data(), cnt));
+    TRY(launch_rk4(s, B, d_q.p, d_p.p, dt, 1, 0.0, d_st.p));
+    TRY(ran("self-check: RK4 kernel failed"));
+    TRY(d_q.get(got.data(), cnt)); TRY(d_p.get(got.data() + cnt, cnt));
+    *rk4_ok = close_enough(got, ref, &usable, "one RK4 step");
   }
+  // what the two adaptive launches below share: one stepHam over (0, ts1), in place on (q, p)
+  auto step_ham = [&](double* dq, double* dp, double ts1, int32_t* status) {
+    RkfCall c;
+    c.q0 = dq; c.p0 = dp; c.qout = dq; c.pout = dp;
+    c.ts1 = ts1;
+    c.row0 = 1; c.inplace = 1; c.gsl_api = s->gsl_api;
+    c.status = status;
+    return c;
+  };
   // ---- RKF45: one accepted sub-step (h = dt, huge tolerances, t: 0 -> dt) ---------------------
-  const bool has_rkf = s->curv->has[K_RKF45];              // (the quad module leaves the adaptive stepper to the wave module)
-  if (rc == HAMK_OK && usable && has_rkf) {
+  if (usable) {
     static const double A[5][5] = {{1.0 / 4, 0, 0, 0, 0},
                                    {3.0 / 32, 9.0 / 32, 0, 0, 0},
                                    {1932.0 / 2197, -7200.0 / 2197, 7296.0 / 2197, 0, 0},
@@ -147,32 +127,27 @@ static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
                                    {-6080.0 / 20520, 41040.0 / 20520, -28352.0 / 20520, 9295.0 / 20520, -5643.0 / 20520}};
     static const double C[6] = {902880.0 / 7618050, 0, 3953664.0 / 7618050, 3855735.0 / 7618050, -1371249.0 / 7618050, 277020.0 / 7618050};
     std::vector<std::vector<double>> ks(6, std::vector<double>(2 * cnt));
-    rc = rhs(y0, ks[0]);
-    for (int sg = 1; sg < 6 && rc == HAMK_OK; ++sg) {
+    TRY(rhs(y0, ks[0]));
+    for (int sg = 1; sg < 6; ++sg) {
       for (size_t i = 0; i < 2 * cnt; ++i) {
         double t = 0.0;
         for (int j2 = 0; j2 < sg; ++j2) t += A[sg - 1][j2] * ks[j2][i];
         yt[i] = y0[i] + dt * t;
       }
-      rc = rhs(yt, ks[sg]);
+      TRY(rhs(yt, ks[sg]));
     }
-    if (rc == HAMK_OK) {
-      for (size_t i = 0; i < 2 * cnt; ++i) {
-        double t = 0.0;
-        for (int j2 = 0; j2 < 6; ++j2) t += C[j2] * ks[j2][i];
-        ref[i] = y0[i] + dt * t;
-      }
-      hipMemcpy(d_q, q.data(), cnt * 8, hipMemcpyHostToDevice); hipMemcpy(d_p, p.data(), cnt * 8, hipMemcpyHostToDevice);
-      double h0 = dt, ea = 1e30, er = 1e30, t0 = 0.0, t1 = dt;
-      int nt = 2, flags = rkf_flags(1, 1, s->gsl_api), max_sub = 8;
-      const double *cq = d_q, *cp = d_p, *cts = nullptr; int32_t* st = d_st; int32_t* ns = nullptr;
-      int ncalls = 1, it_every = 0;
-      void* args[] = {&cq, &cp, &d_q, &d_p, &b, &nt, &cts, &t0, &t1, &h0, &ea, &er, &flags, &max_sub, &st, &ns, &ncalls, &it_every};
-      rc = launch(s, K_RKF45, B, args);
-      if (rc == HAMK_OK && hipStreamSynchronize(s->cur->stream) != hipSuccess) rc = fail(HAMK_ERR_HIP, "self-check: RKF45 kernel failed");
-      hipMemcpy(got.data(), d_q, cnt * 8, hipMemcpyDeviceToHost); hipMemcpy(got.data() + cnt, d_p, cnt * 8, hipMemcpyDeviceToHost);
-      *rkf_ok = close_enough(got, ref, &usable, "one accepted RKF45 sub-step");
+    for (size_t i = 0; i < 2 * cnt; ++i) {
+      double t = 0.0;
+      for (int j2 = 0; j2 < 6; ++j2) t += C[j2] * ks[j2][i];
+      ref[i] = y0[i] + dt * t;
     }
+    TRY(d_q.put(q.data(), cnt)); TRY(d_p.put(p.data(), cnt));
+    RkfCall c = step_ham(d_q.p, d_p.p, dt, d_st.p);
+    c.h0 = dt; c.eps_abs = 1e30; c.eps_rel = 1e30; c.max_sub = 8;
+    TRY(launch_rkf45(s, B, c));
+    TRY(ran("self-check: RKF45 kernel failed"));
+    TRY(d_q.get(got.data(), cnt)); TRY(d_p.get(got.data() + cnt, cnt));
+    *rkf_ok = close_enough(got, ref, &usable, "one accepted RKF45 sub-step");
   }
   if (!usable || flagged) { *rk4_ok = true; *rkf_ok = true; }
   // ---- adaptive stepper end to end ---------------------------------------------------------------
@@ -181,11 +156,11 @@ static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
   // exactly that was seen once -- an unrolled RKF45 body whose results changed from run to run),
   // and both must agree with 64 fixed RK4 steps of T/64 (the kernel checked above) to well within
   // what the controller's tolerance allows.
-  if (rc == HAMK_OK && *rk4_ok && *rkf_ok && usable && !flagged) {
+  if (*rk4_ok && *rkf_ok && usable && !flagged) {
     const int64_t B3 = 4096;                                   // 64 wavefronts: many divergence patterns
     const size_t c3 = (size_t)n * B3;
     const double T = 0.02;
-    std::vector<double> q3(c3), p3(c3), ref3(2 * c3), run[2] = {std::vector<double>(2 * c3), std::vector<double>(2 * c3)};
+    std::vector<double> q3(c3), p3(c3), ref3(2 * c3), ref3b(2 * c3), run[2] = {std::vector<double>(2 * c3), std::vector<double>(2 * c3)};
     std::vector<int32_t> st_ref((size_t)B3), st_run[2] = {std::vector<int32_t>((size_t)B3), std::vector<int32_t>((size_t)B3)},
         ns_run[2] = {std::vector<int32_t>((size_t)B3), std::vector<int32_t>((size_t)B3)};
     for (int j = 0; j < n; ++j)
@@ -195,79 +170,63 @@ static int self_check_once(hamk_system* s, bool* rk4_ok, bool* rkf_ok) {
         q3[(size_t)j * B3 + i] = 0.31 + 0.07 * j + 0.29 * u;
         p3[(size_t)j * B3 + i] = 0.23 - 0.05 * j + 0.29 * w;
       }
-    double *e_q = nullptr, *e_p = nullptr; int32_t *e_st = nullptr, *e_ns = nullptr;
-    bool alloc_ok = hipMalloc((void**)&e_q, c3 * 8) == hipSuccess && hipMalloc((void**)&e_p, c3 * 8) == hipSuccess &&
-                    hipMalloc((void**)&e_st, B3 * 4) == hipSuccess && hipMalloc((void**)&e_ns, B3 * 4) == hipSuccess;
-    long long b3 = B3;
-    auto upload = [&]() { hipMemcpy(e_q, q3.data(), c3 * 8, hipMemcpyHostToDevice); hipMemcpy(e_p, p3.data(), c3 * 8, hipMemcpyHostToDevice); };
-    auto download = [&](std::vector<double>& y) { hipMemcpy(y.data(), e_q, c3 * 8, hipMemcpyDeviceToHost); hipMemcpy(y.data() + c3, e_p, c3 * 8, hipMemcpyDeviceToHost); };
-    if (alloc_ok) {
-      std::vector<double> ref3b(2 * c3);
-      // Between repeated launches a kernel of the module fills every VGPR of every SIMD with launch-dependent
-      // values: a stepping kernel that reads registers it did not write (scripts/probes/sgpr_spill_repro)
-      // agrees with itself back to back and differs once something else has used the registers.
-      auto scribble = [&](unsigned seed) {
-        void* as[] = {&seed};
-        if (hipModuleLaunchKernel(s->mod().fn[K_SCRIBBLE], 2048, 1, 1, 256, 1, 1, 0, s->cur->stream, as, nullptr) != hipSuccess) (void)hipGetLastError();
-      };
-      for (int r = 0; r < 2 && rc == HAMK_OK; ++r) {         // the fixed-step kernel, twice as well
-        scribble(0x9e3779b9u * (unsigned)(r + 1));
-        upload();
-        double ddt = T / 64, no_drift = 0.0; int ns = 64;
-        void* a4[] = {&e_q, &e_p, &b3, &ddt, &ns, &no_drift, &e_st};
-        rc = launch(s, K_RK4, B3, a4);
-        if (rc == HAMK_OK && hipStreamSynchronize(s->cur->stream) != hipSuccess) rc = fail(HAMK_ERR_HIP, "self-check: RK4 kernel failed");
-        download(r == 0 ? ref3 : ref3b);
-      }
-      hipMemcpy(st_ref.data(), e_st, B3 * 4, hipMemcpyDeviceToHost);
-      if (rc == HAMK_OK && std::memcmp(ref3.data(), ref3b.data(), 2 * c3 * 8) != 0) {
-        *rk4_ok = false;
-        g_selfcheck_detail = "two runs of the RK4 kernel on the same input DIFFER";
-      }
-      for (int r = 0; r < 2 && rc == HAMK_OK && has_rkf; ++r) {
-        scribble(0x85ebca6bu * (unsigned)(r + 3));
-        upload();
-        double h0 = T / 100, ea = kRefEpsilon, er = kRefEpsilon, t0 = 0.0, t1 = T;
-        int nt = 2, flags = rkf_flags(1, 1, s->gsl_api), max_sub = 4096;
-        const double *cq = e_q, *cp = e_p, *cts = nullptr;
-        int ncalls = 1, it_every = 0;
-        void* a5[] = {&cq, &cp, &e_q, &e_p, &b3, &nt, &cts, &t0, &t1, &h0, &ea, &er, &flags, &max_sub, &e_st, &e_ns, &ncalls, &it_every};
-        rc = launch(s, K_RKF45, B3, a5);
-        if (rc == HAMK_OK && hipStreamSynchronize(s->cur->stream) != hipSuccess) rc = fail(HAMK_ERR_HIP, "self-check: RKF45 kernel failed");
-        download(run[r]);
-        hipMemcpy(st_run[r].data(), e_st, B3 * 4, hipMemcpyDeviceToHost);
-        hipMemcpy(ns_run[r].data(), e_ns, B3 * 4, hipMemcpyDeviceToHost);
-      }
-      if (rc == HAMK_OK && has_rkf) {
-        bool same = std::memcmp(run[0].data(), run[1].data(), 2 * c3 * 8) == 0 && ns_run[0] == ns_run[1] && st_run[0] == st_run[1];
-        double worst = 0.0;
-        for (int64_t i = 0; i < B3; ++i) {
-          if (st_ref[(size_t)i] != 0 || st_run[0][(size_t)i] != 0) continue;       // outside the system's domain: cannot judge
-          if (ns_run[0][(size_t)i] > 16) continue;       // a hard stretch: 64 RK4 steps are no yardstick there
-          for (int j = 0; j < 2 * n; ++j) {
-            const double a = run[0][(size_t)j * B3 + i], f = ref3[(size_t)j * B3 + i];
-            const double e = std::fabs(a - f) / std::fmax(1.0, std::fabs(f));
-            if (!(e <= worst)) worst = e;
-          }
-        }
-        if (!same || !(worst <= 1e-4)) {
-          *rkf_ok = false;
-          char msg[160];
-          std::snprintf(msg, sizeof msg, "adaptive end-to-end check: two runs %s, worst deviation from 64 RK4 steps %.3g",
-                        same ? "agree" : "DIFFER", worst);
-          g_selfcheck_detail = msg;
-          if (std::getenv("HAMK_SELFCHECK_VERBOSE")) std::fprintf(stderr, "hamk self-check: %s\n", msg);
-        }
+    DevBuf<double> e_q, e_p;
+    DevBuf<int32_t> e_st, e_ns;
+    TRY(e_q.alloc(c3)); TRY(e_p.alloc(c3)); TRY(e_st.alloc((size_t)B3)); TRY(e_ns.alloc((size_t)B3));
+    auto upload = [&]() -> int { TRY(e_q.put(q3.data(), c3)); return e_p.put(p3.data(), c3); };
+    auto download = [&](std::vector<double>& y) -> int { TRY(e_q.get(y.data(), c3)); return e_p.get(y.data() + c3, c3); };
+    // Between repeated launches a kernel of the module fills every VGPR of every SIMD with launch-dependent
+    // values: a stepping kernel that reads registers it did not write (scripts/probes/sgpr_spill_repro)
+    // agrees with itself back to back and differs once something else has used the registers.
+    auto scribble = [&](unsigned seed) { if (launch_scribble(s, seed) != HAMK_OK) (void)hipGetLastError(); };
+    for (int r = 0; r < 2; ++r) {                            // the fixed-step kernel, twice as well
+      scribble(0x9e3779b9u * (unsigned)(r + 1));
+      TRY(upload());
+      TRY(launch_rk4(s, B3, e_q.p, e_p.p, T / 64, 64, 0.0, e_st.p));
+      TRY(ran("self-check: RK4 kernel failed"));
+      TRY(download(r == 0 ? ref3 : ref3b));
+    }
+    TRY(e_st.get(st_ref.data(), (size_t)B3));
+    if (std::memcmp(ref3.data(), ref3b.data(), 2 * c3 * 8) != 0) {
+      *rk4_ok = false;
+      g_selfcheck_detail = "two runs of the RK4 kernel on the same input DIFFER";
+    }
+    for (int r = 0; r < 2; ++r) {
+      scribble(0x85ebca6bu * (unsigned)(r + 3));
+      TRY(upload());
+      RkfCall c = step_ham(e_q.p, e_p.p, T, e_st.p);
+      c.h0 = T / 100; c.max_sub = 4096; c.nsub = e_ns.p;
+      TRY(launch_rkf45(s, B3, c));
+      TRY(ran("self-check: RKF45 kernel failed"));
+      TRY(download(run[r]));
+      TRY(e_st.get(st_run[r].data(), (size_t)B3));
+      TRY(e_ns.get(ns_run[r].data(), (size_t)B3));
+    }
+    bool same = std::memcmp(run[0].data(), run[1].data(), 2 * c3 * 8) == 0 && ns_run[0] == ns_run[1] && st_run[0] == st_run[1];
+    double worst = 0.0;
+    for (int64_t i = 0; i < B3; ++i) {
+      if (st_ref[(size_t)i] != 0 || st_run[0][(size_t)i] != 0) continue;       // outside the system's domain: cannot judge
+      if (ns_run[0][(size_t)i] > 16) continue;       // a hard stretch: 64 RK4 steps are no yardstick there
+      for (int j = 0; j < 2 * n; ++j) {
+        const double a = run[0][(size_t)j * B3 + i], f = ref3[(size_t)j * B3 + i];
+        const double e = std::fabs(a - f) / std::fmax(1.0, std::fabs(f));
+        if (!(e <= worst)) worst = e;
       }
     }
-    hipFree(e_q); hipFree(e_p); hipFree(e_st); hipFree(e_ns);
-    (void)hipGetLastError();
+    if (!same || !(worst <= 1e-4)) {
+      *rkf_ok = false;
+      char msg[160];
+      std::snprintf(msg, sizeof msg, "adaptive end-to-end check: two runs %s, worst deviation from 64 RK4 steps %.3g",
+                    same ? "agree" : "DIFFER", worst);
+      g_selfcheck_detail = msg;
+      if (std::getenv("HAMK_SELFCHECK_VERBOSE")) std::fprintf(stderr, "hamk self-check: %s\n", msg);
+    }
   }
   if (const char* e = test_env("HAMK_SELFCHECK_FAULT")) {        // test hook: pretend the unrolled body is wrong
     if (std::strstr(e, "rk4") && !s->curv->desc.rk4_stage_loop) *rk4_ok = false;
     if (std::strstr(e, "rkf") && !s->curv->desc.rkf_stage_loop) *rkf_ok = false;
   }
-  return rc;
+  return HAMK_OK;
 }
 
 static void derive_body_fields(const hamk_system* s, SystemDesc& d);
@@ -312,7 +271,7 @@ static int load_modules(hamk_system* s) {
   HIP_TRY(hipModuleLoadData(&d->module, v->code.data()));
   if (!v->code2.empty()) HIP_TRY(hipModuleLoadData(&d->module2, v->code2.data()));
   for (int k = 0; k < K__COUNT; ++k)
-    if (v->has[k]) HIP_TRY(hipModuleGetFunction(&d->fn[k], (v->use2[k] && d->module2) ? d->module2 : d->module, kKernelNames[k]));
+    HIP_TRY(hipModuleGetFunction(&d->fn[k], (v->use2[k] && d->module2) ? d->module2 : d->module, kKernelNames[k]));
   d->code_generation = v->generation;
   return HAMK_OK;
 }
@@ -339,18 +298,14 @@ int current_device_state(hamk_system* s) {
   return HAMK_OK;
 }
 
-int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out);
-std::string check_options(const hamk_options& o, int n);
-std::string check_options(const hamk_options& o, const SystemDesc& base);
-
 // Everything a call over B trajectories needs in place: the device state, the specialisation chosen for (n, B) --
 // built on first use --, its modules loaded on this device and self-checked.
-int bind_device(hamk_system* s, int64_t B, int kernel) {
-  TRY0(current_device_state(s));
-  TRY0(variant_for(s, B, kernel, &s->curv));
+int bind_device(hamk_system* s, int64_t B) {
+  TRY(current_device_state(s));
+  TRY(variant_for(s, B, &s->curv));
   DevModule& m = s->mod();
   if (m.module && m.code_generation == s->curv->generation) return HAMK_OK;
-  TRY0(load_modules(s));
+  TRY(load_modules(s));
   return self_check(s);
 }
 
@@ -362,13 +317,43 @@ static int64_t trajectories_per_block(const Variant* v) {
   return 256;
 }
 
-int launch(hamk_system* s, KernelId k, int64_t B, void** args) {
-  const unsigned block = 256;
-  const int64_t per_block = trajectories_per_block(s->curv);
-  const int64_t grid = (B + per_block - 1) / per_block;
-  if (grid > 0x7fffffffLL) return fail(HAMK_ERR_INVALID, "ensemble too large for one launch");
-  HIP_TRY(hipModuleLaunchKernel(s->mod().fn[k], (unsigned)grid, 1, 1, block, 1, 1, 0, s->cur->stream, args, nullptr));
-  return HAMK_OK;
+// ---- the typed launchers (hamk_host.h) ---------------------------------------------------------------------------------
+template <class Sig, class... A> static int launch_path(hamk_system* s, KernelId k, int64_t B, A... a) {
+  return launch_kernel<Sig>::on(s->mod().fn[k], s->cur->stream, B, trajectories_per_block(s->curv), a...);
+}
+int launch_rk4(hamk_system* s, int64_t B, double* q, double* p, double dt, int nsteps, double drift_tol, int* status) {
+  return launch_path<sig::hamk_rk4_steps_k>(s, K_RK4, B, q, p, B, dt, nsteps, drift_tol, status);
+}
+int launch_hameqs(hamk_system* s, int64_t B, const double* q, const double* p, double* dq, double* dp, int* status) {
+  return launch_path<sig::hamk_hameqs_k>(s, K_HAMEQS, B, q, p, dq, dp, B, status);
+}
+int launch_coords(hamk_system* s, int64_t B, const double* q, double* x) { return launch_path<sig::hamk_coords_k>(s, K_COORDS, B, q, x, B); }
+int launch_to_phase(hamk_system* s, int64_t B, const double* q, const double* qd, double* p) {
+  return launch_path<sig::hamk_to_phase_k>(s, K_TO_PHASE, B, q, qd, p, B);
+}
+int launch_from_phase(hamk_system* s, int64_t B, const double* q, const double* p, double* qd, int* status) {
+  return launch_path<sig::hamk_from_phase_k>(s, K_FROM_PHASE, B, q, p, qd, B, status);
+}
+int launch_observe(hamk_system* s, int64_t B, const double* q, const double* p, double* ke, double* pe, double* h, int* status) {
+  return launch_path<sig::hamk_observe_k>(s, K_OBSERVE, B, q, p, ke, pe, h, B, status);
+}
+int launch_observe_config(hamk_system* s, int64_t B, const double* q, const double* qd, double* ke, double* lag) {
+  return launch_path<sig::hamk_observe_config_k>(s, K_OBSERVE_CFG, B, q, qd, ke, lag, B);
+}
+// the flags argument of hamk_rkf45_k (hamk_device.hpp rkf45_body)
+static int rkf_flags(int row0, int inplace, int gsl_api) { return (row0 & 1) | ((inplace & 3) << 8) | ((gsl_api & 3) << 16); }
+int launch_rkf45(hamk_system* s, int64_t B, const RkfCall& c) {
+  return launch_path<sig::hamk_rkf45_k>(s, K_RKF45, B, c.q0, c.p0, c.qout, c.pout, B, c.nt, c.ts, c.ts0, c.ts1, c.h0, c.eps_abs, c.eps_rel,
+                                        rkf_flags(c.row0, c.inplace, c.gsl_api), c.max_sub, c.status, c.nsub, c.ncalls, c.it_every);
+}
+int launch_scribble(hamk_system* s, unsigned seed) {
+  return launch_kernel<sig::hamk_scribble_k>::on(s->mod().fn[K_SCRIBBLE], s->cur->stream, 2048 * 256, 256, seed);
+}
+int launch_symp(hamk_system* s, int64_t B, double* q, double* p, int nsteps, int nsub, double ha, double hb, int iters, double* residual, int* status) {
+  return launch_kernel<sig::hamk_symp_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].symp_fn, s->cur->stream, B, 256, q, p, B, nsteps, nsub, ha, hb, iters, residual, status);
+}
+int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx) {
+  return launch_kernel<sig::hamk_sample_k>::on(d->sample_fn, d->stream, B, 256, q, qd, B, first_index, seed, n, bx);
 }
 
 // ---------------------------------------------------------------------------
@@ -433,15 +418,6 @@ std::string check_options(const hamk_options& o, const SystemDesc& base) {
   return std::string();
 }
 
-// Which lanes serve a trajectory for an ensemble of B (hamk_options::mapping = HAMK_AUTO).
-// The lane kernels do the least work per trajectory (compile-time sparsity of the seeds, everything in registers) but
-// put 64 trajectories in a wavefront: below ~64 x 1024 SIMDs trajectories they leave SIMDs idle, and for the systems
-// whose lane kernel is large the wave-cooperative kernels (4 trajectories per wavefront at n <= 16) then win.
-// Thresholds measured on MI355X (scripts/sweep_batch.py -> profiles/r03_throughput_vs_B*.jsonl, DESIGN.md section 2).
-// Which kernels the quad module (hamk_quad.hpp) provides: all eight since the second half of round 3.  The per-kernel
-// dispatch stays: a module that lacks a kernel leaves it to the module that serves the system's size otherwise.
-static bool quad_has(int kernel) { (void)kernel; return true; }      // (the first version provided the four kernels of the hot path only)
-
 // Can a lane run the per-trajectory first-order sweep of this system with compile-time seeds?  It keeps one register pair
 // per DISTINCT entry of the Jacobian (hamk_codegen.cpp distinct_jacobian_entries): 2n for a chain, m n for a dense map.
 static bool quad_eligible(hamk_system* s) {
@@ -475,21 +451,24 @@ static bool inertia_positive(const hamk_system* s) {
   return true;
 }
 
-static int choose_mapping(hamk_system* s, int64_t B, int kernel) {
+// Which lanes serve a trajectory for an ensemble of B (hamk_options::mapping = HAMK_AUTO).
+// The lane kernels do the least work per trajectory (compile-time sparsity of the seeds, everything in registers) but
+// put 64 trajectories in a wavefront: below ~64 x 1024 SIMDs trajectories they leave SIMDs idle, and for the systems
+// whose lane kernel is large the wave-cooperative kernels (4 trajectories per wavefront at n <= 16) then win.
+// Thresholds measured on MI355X (scripts/sweep_batch.py -> profiles/r03_throughput_vs_B*.jsonl, DESIGN.md section 2).
+static int choose_mapping(hamk_system* s, int64_t B) {
   const int n = s->base.n;
-  const int rest = n > 16 ? HAMK_MAP_WAVE : HAMK_MAP_LANE;  // where the kernels the quad module lacks run
-  if (s->opt.mapping != HAMK_AUTO) return (s->opt.mapping == HAMK_MAP_QUAD && !quad_has(kernel)) ? rest : s->opt.mapping;
+  if (s->opt.mapping != HAMK_AUTO) return s->opt.mapping;
   if (s->ensemble_size > 0) B = s->ensemble_size;           // the launch is a piece of a larger ensemble: one mapping for all pieces
   bool w = false;
   const bool pos = inertia_positive(s);
-  if (pos && env_flag("HAMK_QUAD", &w) && w && n <= 32) return quad_has(kernel) ? HAMK_MAP_QUAD : rest;      // tests / experiments
+  if (pos && env_flag("HAMK_QUAD", &w) && w && n <= 32) return HAMK_MAP_QUAD;      // tests / experiments
   const bool no_quad = !pos || (env_flag("HAMK_QUAD", &w) && !w);
   if (env_flag("HAMK_WAVE", &w)) return (w || n > 16) ? HAMK_MAP_WAVE : HAMK_MAP_LANE;
   if (n > 32) return HAMK_MAP_WAVE;
-  if (n > 16) return (!no_quad && quad_has(kernel) && (quad_eligible(s) || quad_dense_eligible(s))) ? HAMK_MAP_QUAD : HAMK_MAP_WAVE;
+  if (n > 16) return (!no_quad && (quad_eligible(s) || quad_dense_eligible(s))) ? HAMK_MAP_QUAD : HAMK_MAP_WAVE;
   const int64_t below = quad_below(n);                      // ensembles smaller than this leave the lane kernels
-  if (B < below && !no_quad && quad_eligible(s)) return quad_has(kernel) ? HAMK_MAP_QUAD : HAMK_MAP_LANE;
-  return HAMK_MAP_LANE;
+  return (B < below && !no_quad && quad_eligible(s)) ? HAMK_MAP_QUAD : HAMK_MAP_LANE;
 }
 
 // What follows from the choice of stepping bodies.  make_desc ends with it; the two places that switch a built variant to the
@@ -682,11 +661,11 @@ static int post_build_checks(hamk_system* s, Variant* v) {
   return HAMK_OK;
 }
 
-static int variant_of(hamk_system* s, int mapping, int64_t B, int kernel, Variant** out);
-int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out) { return variant_of(s, choose_mapping(s, B, kernel), B, kernel, out); }
-int lane_variant(hamk_system* s, Variant** out) { return variant_of(s, HAMK_MAP_LANE, INT64_MAX, K_HAMEQS, out); }
+static int variant_of(hamk_system* s, int mapping, int64_t B, Variant** out);
+int variant_for(hamk_system* s, int64_t B, Variant** out) { return variant_of(s, choose_mapping(s, B), B, out); }
+int lane_variant(hamk_system* s, Variant** out) { return variant_of(s, HAMK_MAP_LANE, INT64_MAX, out); }
 
-static int variant_of(hamk_system* s, const int mapping, int64_t B, int kernel, Variant** out) {
+static int variant_of(hamk_system* s, const int mapping, int64_t B, Variant** out) {
   if (s->var[mapping]) { *out = s->var[mapping]; return HAMK_OK; }
   Variant* v = new Variant();
   v->mapping = mapping;
@@ -720,10 +699,9 @@ static int variant_of(hamk_system* s, const int mapping, int64_t B, int kernel, 
         vgpr_spill_count(v->use2[K_RK4] ? v->code2 : v->code, kKernelNames[K_RK4]) > 768) {
       s->quad_dense_eligible = 0;
       delete v;
-      return variant_for(s, B, kernel, out);
+      return variant_for(s, B, out);
     }
   }
-  for (int k = 0; k < K__COUNT; ++k) v->has[k] = mapping != HAMK_MAP_QUAD || quad_has(k);
   s->var[mapping] = v;
   *out = v;
   return HAMK_OK;

@@ -1,8 +1,11 @@
 // hamk_host.h -- what the three host translation units of libhamk.so share (round 4: hamk_api.cpp split):
 //   hamk_build.cpp     generated source -> gfx950 code objects: hiprtc, the on-disk cache, the two builds per module
 //   hamk_dispatch.cpp  options -> specialisations (which lanes serve a trajectory, bodies, sincos policy ...), device
-//                      binding, launches, the first-use self-check
+//                      binding, the typed launchers (launch_*), the first-use self-check
 //   hamk_api.cpp       the C ABI of include/hamk.h: argument checks, host-pointer staging, checkpoints
+// and the ONE host-side statement of every kernel's parameter list (namespace sig below): launch_kernel<Sig> builds the argument
+// array from it and is the only caller of hipModuleLaunchKernel; tests/test_kernel_signatures.py holds the table against the
+// device headers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,7 +33,6 @@ const std::string& last_error_text();
     if (e_ != hipSuccess)                                                                      \
       return hamk_host::fail(HAMK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
-#define TRY0(expr) do { int rc0_ = (expr); if (rc0_ != HAMK_OK) return rc0_; } while (0)
 #define TRY(expr) do { int rc_ = (expr); if (rc_ != HAMK_OK) return rc_; } while (0)
 
 enum KernelId { K_RK4, K_HAMEQS, K_COORDS, K_TO_PHASE, K_FROM_PHASE, K_OBSERVE, K_OBSERVE_CFG, K_RKF45, K_SCRIBBLE, K__COUNT };
@@ -105,7 +107,6 @@ struct Variant {
   int generation = 0;          // bumped whenever `code` is rebuilt (the self-check's recovery path)
   int self_check_rebuilds = 0;
   bool forced_rk4_body = false, forced_rkf_body = false;
-  bool has[K__COUNT] = {};     // the kernels this module provides (the quad module: four of the eight)
   // the lane variant's COMPANION module (hamk_symp.hpp: hamk_symp_steps_k), built the first time hamk_symplectic_* asks for it;
   // its own source, code object and one-line description -- no part of `source`, `code`, `build_info` or the kernel counts above
   std::string symp_source;
@@ -202,6 +203,63 @@ struct hamk_system {
 
 namespace hamk_host {
 
+// ---- the kernels' signatures -------------------------------------------------------------------------------------------
+// One function type per kernel: the eight of the path (HAMK_INSTANTIATE / _QUAD / _WAVE state the same eight), hamk_scribble_k,
+// the companion module's stepper (hamk_symp.hpp) and the sampler (hamk_sample.hpp).
+struct HamkBoxes { double q_lo[64], q_hi[64], qd_lo[64], qd_hi[64]; };      // = hamk_sample.hpp; travels by value
+static_assert(sizeof(HamkBoxes) == 4 * 64 * sizeof(double), "HamkBoxes is hamk_sample_k's last argument, byte for byte");
+namespace sig {
+using hamk_rk4_steps_k = void(double*, double*, long long, double, int, double, int*);
+using hamk_hameqs_k = void(const double*, const double*, double*, double*, long long, int*);
+using hamk_coords_k = void(const double*, double*, long long);
+using hamk_to_phase_k = void(const double*, const double*, double*, long long);
+using hamk_from_phase_k = void(const double*, const double*, double*, long long, int*);
+using hamk_observe_k = void(const double*, const double*, double*, double*, double*, long long, int*);
+using hamk_observe_config_k = void(const double*, const double*, double*, double*, long long);
+using hamk_rkf45_k = void(const double*, const double*, double*, double*, long long, int, const double*, double, double, double, double, double, int, int, int*, int*, int, int);
+using hamk_scribble_k = void(unsigned);
+using hamk_symp_steps_k = void(double*, double*, long long, int, int, double, double, int, double*, int*);
+using hamk_sample_k = void(double*, double*, long long, long long, unsigned long long, int, HamkBoxes);
+}  // namespace sig
+
+// A launch over B trajectories, per_block of them to a block of 256 threads.  The arguments arrive BY VALUE as the signature's own
+// parameter types -- the compiler converts or refuses -- and the argument array is built from them here, nowhere else.
+template <class Sig> struct launch_kernel;
+template <class... P> struct launch_kernel<void(P...)> {
+  static int on(hipFunction_t fn, hipStream_t stream, int64_t B, int64_t per_block, P... p) {
+    const int64_t grid = (B + per_block - 1) / per_block;
+    if (grid > 0x7fffffffLL) return fail(HAMK_ERR_INVALID, "ensemble too large for one launch");
+    void* args[] = {&p...};
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+    return HAMK_OK;
+  }
+};
+
+constexpr double kRefEps = 1.49012e-08;                     // Hamilton.hs:448
+// hamk_rkf45_k's arguments by name (five adjacent doubles, four adjacent ints): a call site states what differs from these
+struct RkfCall {
+  const double *q0 = nullptr, *p0 = nullptr;
+  double *qout = nullptr, *pout = nullptr;
+  int nt = 2;
+  const double* ts = nullptr;                               // the time grid beyond two times; else (ts0, ts1) travel as arguments
+  double ts0 = 0.0, ts1 = 0.0, h0 = 0.0, eps_abs = kRefEps, eps_rel = kRefEps;
+  int row0 = 0, inplace = 0, gsl_api = 2;                   // packed into the kernel's flags (rkf_flags; hamk_device.hpp rkf45_body)
+  int max_sub = 0;
+  int *status = nullptr, *nsub = nullptr;
+  int ncalls = 1, it_every = 0;
+};
+
+// Device memory of the first-use self-checks: released on every path out, every copy's result looked at.
+template <class T> struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  ~DevBuf() { if (p) hipFree(p); }
+  int alloc(size_t count) { HIP_TRY(hipMalloc((void**)&p, count * sizeof(T))); return HAMK_OK; }
+  int put(const T* host, size_t count) { HIP_TRY(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice)); return HAMK_OK; }
+  int get(T* host, size_t count) const { HIP_TRY(hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost)); return HAMK_OK; }
+};
+
 // ---- hamk_build.cpp ---------------------------------------------------------------------------------------------------
 int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, bool symp = false);
 int build_symp(Variant* v, bool cache_on);                 // the lane variant's companion module (hamk_symp.hpp), once
@@ -216,11 +274,22 @@ int sample_code(bool cache_on, const std::vector<char>** out);        // hamk_sa
 std::string check_options(const hamk_options& o, int n);
 std::string check_options(const hamk_options& o, const SystemDesc& base);      // what depends on the system: the dense quad path's capacity
 int build_force(const hamk_system* s);
-int variant_for(hamk_system* s, int64_t B, int kernel, Variant** out);
+int variant_for(hamk_system* s, int64_t B, Variant** out);
 int lane_variant(hamk_system* s, Variant** out);            // the one-trajectory-per-lane specialisation, whatever B (n <= 16)
 int current_device_state(hamk_system* s);
-int bind_device(hamk_system* s, int64_t B, int kernel);
-int launch(hamk_system* s, KernelId k, int64_t B, void** args);
-int rkf_flags(int row0, int inplace, int gsl_api);
+int bind_device(hamk_system* s, int64_t B);
+// the typed launchers: the path kernels of the bound variant (bind_device) on the handle's stream, B trajectories each ...
+int launch_rk4(hamk_system* s, int64_t B, double* q, double* p, double dt, int nsteps, double drift_tol, int* status);
+int launch_hameqs(hamk_system* s, int64_t B, const double* q, const double* p, double* dq, double* dp, int* status);
+int launch_coords(hamk_system* s, int64_t B, const double* q, double* x);
+int launch_to_phase(hamk_system* s, int64_t B, const double* q, const double* qd, double* p);
+int launch_from_phase(hamk_system* s, int64_t B, const double* q, const double* p, double* qd, int* status);
+int launch_observe(hamk_system* s, int64_t B, const double* q, const double* p, double* ke, double* pe, double* h, int* status);
+int launch_observe_config(hamk_system* s, int64_t B, const double* q, const double* qd, double* ke, double* lag);
+int launch_rkf45(hamk_system* s, int64_t B, const RkfCall& c);
+int launch_scribble(hamk_system* s, unsigned seed);         // 2048 blocks, whatever the mapping
+// ... the companion module's stepper (loaded by hamk_symplectic_steps) and the sampler (loaded by hamk_sample_batch): one lane each
+int launch_symp(hamk_system* s, int64_t B, double* q, double* p, int nsteps, int nsub, double ha, double hb, int iters, double* residual, int* status);
+int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx);
 
 }  // namespace hamk_host
