@@ -47,6 +47,7 @@ module Numeric.Hamilton.HIP
   , iterateStepHamBatch
   , rk4StepsBatch
   , symplecticStepsBatch
+  , lyapunovStepsBatch
   , evolveHamEnsemble
     -- * ensembles resident in HBM, several GPUs from one process
   , DeviceEnsemble
@@ -209,6 +210,9 @@ foreign import ccall safe "hamk_rk4_steps_checked"
 foreign import ccall safe "hamk_symplectic_steps"
   c_symplectic_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32 -> Int32 -> Ptr Double
                      -> Ptr Int32 -> Int32 -> IO CInt
+foreign import ccall safe "hamk_lyapunov_steps"
+  c_lyapunov_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32
+                   -> Double -> Ptr Double -> Ptr Int32 -> Int32 -> IO CInt
 foreign import ccall safe "hamk_checkpoint_write"
   c_ck_write :: CString -> Int32 -> Int64 -> Ptr Double -> Ptr Double -> Int32 -> Int64 -> Word64 -> Double -> IO CInt
 foreign import ccall safe "hamk_checkpoint_info"
@@ -509,6 +513,21 @@ symplecticStepsBatch :: forall m n. KnownNat n => Double -> Int -> Int -> Int ->
 symplecticStepsBatch dt k order iters (HipSystem h) e = withForeignPtr h $ \s ->
   inPlace e (\b pq pp -> c_symplectic_steps s b pq pp dt (fromIntegral k) (fromIntegral order) (fromIntegral iters) nullPtr nullPtr memHost)
     "symplecticSteps"
+
+-- | Largest-Lyapunov-exponent stepping fused with RK4 (no counterpart in the reference; Benettin's two-trajectory method):
+--   @k@ intervals of @every@ RK4 steps of @dt@, the shadow trajectory @y + d0 w@ renormalised after each.  The deviation @w@
+--   (an ensemble: positions = wq, momenta = wp) is used as it is -- a unit vector is the caller's business -- and, with the
+--   running @logsum@, carries a run over several calls bit for bit.  Returns (state, w, logsum); the exponent estimate is
+--   @logsum / (k * every * dt)@.  One trajectory per lane: @n <= 16@.
+lyapunovStepsBatch :: forall m n. KnownNat n => Double -> Int -> Int -> Double -> HipSystem m n -> Ensemble n -> Ensemble n
+                   -> VS.Vector Double -> IO (Ensemble n, Ensemble n, VS.Vector Double)
+lyapunovStepsBatch dt k every d0 (HipSystem h) e w logsum = withForeignPtr h $ \s -> do
+  wq <- VS.thaw (ensPositions w); wp <- VS.thaw (ensMomenta w); ls <- VS.thaw logsum
+  e' <- VSM.unsafeWith wq $ \pwq -> VSM.unsafeWith wp $ \pwp -> VSM.unsafeWith ls $ \pls ->
+    inPlace e (\b pq pp -> c_lyapunov_steps s b pq pp pwq pwp dt (fromIntegral k) (fromIntegral every) d0 pls nullPtr memHost)
+      "lyapunovSteps"
+  w' <- Ensemble (ensSize w) <$> VS.unsafeFreeze wq <*> VS.unsafeFreeze wp
+  (,,) e' w' <$> VS.unsafeFreeze ls
 
 -- | 'evolveHam' (Hamilton.hs:433-462) for every member: one ensemble per requested time,
 --   element 0 being the initial ensemble.

@@ -241,7 +241,7 @@ class System:
         text = fn(self._h)
         if text is None:
             msg = _abi.lib().hamk_last_error().decode("utf-8", "replace")
-            unsupported = msg.startswith("the symplectic stepper") or "unsupported" in msg
+            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper")) or "unsupported" in msg
             raise HamkError(_abi.HAMK_ERR_UNSUPPORTED if unsupported else _abi.HAMK_ERR_COMPILE, msg)
         return text.decode()
 
@@ -254,6 +254,16 @@ class System:
     def symplectic_build_info(self) -> str:
         """One `build_info`-format line for hamk_symp_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs."""
         return self._symplectic_text(_abi.lib().hamk_symplectic_build_info)
+
+    @property
+    def lyapunov_source(self) -> str:
+        """Source of the Lyapunov stepper's companion module (hamk_lyapunov_source; builds it if needed, needs no GPU)."""
+        return self._symplectic_text(_abi.lib().hamk_lyapunov_source)
+
+    @property
+    def lyapunov_build_info(self) -> str:
+        """One `build_info`-format line for hamk_lyap_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
+        return self._symplectic_text(_abi.lib().hamk_lyapunov_build_info)
 
     def kernel_bytes(self, kernel: str) -> int:
         return int(_abi.lib().hamk_system_kernel_bytes(self._h, kernel.encode()))
@@ -579,6 +589,48 @@ def symplecticSteps(dt: float, nsteps: int, s: System, ph: Phase, order: int = 2
     s._after(st, qa.single, "symplecticSteps")
     out = Phase(_shape_out(q, qa.single), _shape_out(p, qa.single))
     return (out, _shape_out(res, qa.single)) if with_residual else out
+
+
+def lyapunovSteps(dt: float, nintervals: int, every: int, s: System, ph: Phase, w: Optional[Phase] = None, d0: float = 1e-7,
+                  logsum=None, inplace: bool = False):
+    """Largest-Lyapunov-exponent stepping fused with RK4 (hamk_lyapunov_steps; no reference counterpart; Benettin's
+    two-trajectory method): `nintervals` intervals of `every` RK4 steps of `dt`, the shadow trajectory y + d0 w renormalised
+    after each.  Returns (Phase, w, logsum): the new state, the new deviation as a Phase-shaped pair (its `positions` /
+    `momenta` are wq / wp) and the running sum of log(d / d0); the exponent estimate is logsum / (nintervals * every * dt).
+    w=None: every component 1 / sqrt(2n); a given w is used as it is (a unit vector is the caller's business).
+    logsum=None: zeros.  Feeding the returned w and logsum to the next call continues the run bit for bit.  inplace=True
+    advances the given arrays (state, and w / logsum where given) without copying.  One trajectory per lane: n <= 16."""
+    qa, pa = _pair(ph.positions, "positions", ph.momenta, "momenta", s.n)
+    if inplace:
+        _in_place(qa, ph.positions, "positions"); _in_place(pa, ph.momenta, "momenta")
+    q, p = (qa.a, pa.a) if inplace else (qa.clone(), pa.clone())
+    if w is None:
+        wq, wp = qa.like(s.n), qa.like(s.n)
+        wq[...] = 1.0 / np.sqrt(2.0 * s.n); wp[...] = 1.0 / np.sqrt(2.0 * s.n)
+    else:
+        wqa, wpa = _pair(w.positions, "w.positions", w.momenta, "w.momenta", s.n)
+        if wqa.B != qa.B or wqa.device != qa.device or (qa.device and wqa.a.device != qa.a.device):
+            raise ValueError("w must describe the ensemble of the state, in the same memory")
+        if inplace:
+            _in_place(wqa, w.positions, "w.positions"); _in_place(wpa, w.momenta, "w.momenta")
+        wq, wp = (wqa.a, wpa.a) if inplace else (wqa.clone(), wpa.clone())
+    if logsum is None:
+        ls = qa.like(None, zero=True)
+    else:
+        la = _Arr(logsum.reshape(1, -1) if _is_torch(logsum) else np.asarray(logsum, dtype=np.float64).reshape(1, -1), 1, "logsum")
+        if la.B != qa.B or la.device != qa.device or (qa.device and la.a.device != qa.a.device):
+            raise ValueError(f"logsum: expected {qa.B} values in the memory of the state")
+        if inplace:
+            _in_place(la, logsum, "logsum")
+        ls = (la.a if inplace else la.clone()).reshape(qa.B)
+    # zeroed: with nothing to do (nintervals = 0, an empty ensemble) the call returns HAMK_OK without writing status
+    st = qa.like(None, "i4", zero=True)
+    with s._on(qa):
+        _abi.check(_abi.lib().hamk_lyapunov_steps(s._h, qa.B, _ptr(q), _ptr(p), _ptr(wq), _ptr(wp), float(dt), int(nintervals), int(every),
+                                                  float(d0), _ptr(ls), _ptr(st), qa.mem))
+    s._after(st, qa.single, "lyapunovSteps")
+    return (Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Phase(_shape_out(wq, qa.single), _shape_out(wp, qa.single)),
+            _shape_out(ls, qa.single))
 
 
 # ---------------------------------------------------------------------------------------

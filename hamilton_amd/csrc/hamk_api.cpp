@@ -707,30 +707,43 @@ int hamk_rk4_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, i
   return hamk_rk4_steps_checked(s, B, q, p, dt, nsteps, 0.0, status, mem);
 }
 
-// ---- symplectic fixed-step stepping (hamk_symp.hpp) -------------------------------------------------------------------
-// The lane variant of a handle that can run the stepper, its companion module built: n <= 16 and no other mapping stated.
-// AUTO never leaves the lane mapping here, whatever B is (its small-ensemble rule for 11 <= n <= 16 was measured on RK4).
-static int symp_variant(hamk_system* s, Variant** out) {
+// ---- the lane variant's companion modules: symplectic stepping (hamk_symp.hpp), Lyapunov stepping (hamk_lyap.hpp) --------
+// The lane variant of a handle that can run a companion's stepper, that companion module built: n <= 16 and no other mapping
+// stated.  AUTO never leaves the lane mapping here, whatever B is (its small-ensemble rule for 11 <= n <= 16 was measured on RK4).
+static int companion_variant(hamk_system* s, CompanionKind kind, Variant** out) {
+  const std::string what = kind == COMPANION_SYMP ? "the symplectic stepper" : "the Lyapunov stepper";
   if (s->base.n > 16)
-    return fail(HAMK_ERR_UNSUPPORTED, "the symplectic stepper runs one trajectory per lane: n <= 16 (this system has n = " + std::to_string(s->base.n) + ")");
+    return fail(HAMK_ERR_UNSUPPORTED, what + " runs one trajectory per lane: n <= 16 (this system has n = " + std::to_string(s->base.n) + ")");
   if (s->opt.mapping == HAMK_MAP_QUAD || s->opt.mapping == HAMK_MAP_WAVE)
-    return fail(HAMK_ERR_UNSUPPORTED, std::string("the symplectic stepper runs one trajectory per lane (n <= 16, HAMK_MAP_LANE): this handle's options state ") +
+    return fail(HAMK_ERR_UNSUPPORTED, what + " runs one trajectory per lane (n <= 16, HAMK_MAP_LANE): this handle's options state " +
                                           (s->opt.mapping == HAMK_MAP_QUAD ? "HAMK_MAP_QUAD" : "HAMK_MAP_WAVE"));
   TRY(lane_variant(s, out));
-  return build_symp(*out, s->cache_on);
+  return build_companion(*out, kind, s->cache_on);
 }
 
-const char* hamk_symplectic_source(hamk_system* s) {
-  Variant* v = nullptr;
-  if (!s) { fail(HAMK_ERR_INVALID, "null system handle"); return nullptr; }
-  return symp_variant(s, &v) == HAMK_OK ? v->symp_source.c_str() : nullptr;
+// the companion's kernel on the current device, its module loaded beside the lane module the first time
+static int companion_load(hamk_system* s, const Variant* v, CompanionKind kind) {
+  TRY(current_device_state(s));
+  DevModule& m = s->cur->mod[HAMK_MAP_LANE];
+  if (!m.companion_fn[kind]) {
+    if (m.companion_module[kind]) { hipModuleUnload(m.companion_module[kind]); m.companion_module[kind] = nullptr; }
+    HIP_TRY(hipModuleLoadData(&m.companion_module[kind], v->companion[kind].code.data()));
+    HIP_TRY(hipModuleGetFunction(&m.companion_fn[kind], m.companion_module[kind], companion_kernel_name(kind)));
+  }
+  return HAMK_OK;
 }
 
-const char* hamk_symplectic_build_info(hamk_system* s) {
+static const char* companion_text(hamk_system* s, CompanionKind kind, bool info) {
   Variant* v = nullptr;
   if (!s) { fail(HAMK_ERR_INVALID, "null system handle"); return nullptr; }
-  return symp_variant(s, &v) == HAMK_OK ? v->symp_info.c_str() : nullptr;
+  if (companion_variant(s, kind, &v) != HAMK_OK) return nullptr;
+  return info ? v->companion[kind].info.c_str() : v->companion[kind].source.c_str();
 }
+
+const char* hamk_symplectic_source(hamk_system* s) { return companion_text(s, COMPANION_SYMP, false); }
+const char* hamk_symplectic_build_info(hamk_system* s) { return companion_text(s, COMPANION_SYMP, true); }
+const char* hamk_lyapunov_source(hamk_system* s) { return companion_text(s, COMPANION_LYAP, false); }
+const char* hamk_lyapunov_build_info(hamk_system* s) { return companion_text(s, COMPANION_LYAP, true); }
 
 int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t order,
                           int32_t iters, double* residual, int32_t* status, int32_t mem) {
@@ -741,15 +754,9 @@ int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, doubl
   if (iters < 0 || iters > 64) return fail(HAMK_ERR_INVALID, "iters must be 1 .. 64, or HAMK_AUTO (8)");
   if (!std::isfinite(dt)) return fail(HAMK_ERR_INVALID, "dt is not finite");
   Variant* v = nullptr;
-  TRY(symp_variant(s, &v));
+  TRY(companion_variant(s, COMPANION_SYMP, &v));
   if (B == 0 || nsteps == 0) return HAMK_OK;
-  TRY(current_device_state(s));
-  DevModule& m = s->cur->mod[HAMK_MAP_LANE];
-  if (!m.symp_fn) {
-    if (m.symp_module) { hipModuleUnload(m.symp_module); m.symp_module = nullptr; }
-    HIP_TRY(hipModuleLoadData(&m.symp_module, v->symp_code.data()));
-    HIP_TRY(hipModuleGetFunction(&m.symp_fn, m.symp_module, "hamk_symp_steps_k"));
-  }
+  TRY(companion_load(s, v, COMPANION_SYMP));
   // order 4: substeps g1 dt, g2 dt, g1 dt with g1 = 1 / (2 - 2^(1/3)), g2 = 1 - 2 g1 (negative: the middle substep goes back)
   const double g1 = 1.0 / (2.0 - std::pow(2.0, 1.0 / 3.0)), g2 = 1.0 - 2.0 * g1;
   const double ha = order == 4 ? g1 * dt : dt, hb = order == 4 ? g2 * dt : 0.0;
@@ -761,6 +768,32 @@ int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, doubl
   TRY(st.out(residual, (size_t)B, &xr));
   TRY(st.out(status, (size_t)B, &dst));
   TRY(launch_symp(s, B, xq, xp, nsteps, order == 4 ? 3 : 1, ha, hb, iters == HAMK_AUTO ? 8 : iters, xr, dst));
+  return st.finish();
+}
+
+int hamk_lyapunov_steps(hamk_system* s, int64_t B, double* q, double* p, double* wq, double* wp, double dt, int32_t nintervals,
+                        int32_t every, double d0, double* logsum, int32_t* status, int32_t mem) {
+  TRY(check_call(s, B, mem));
+  if (!q || !p || !wq || !wp || !logsum) return fail(HAMK_ERR_INVALID, "null q / p / wq / wp / logsum");
+  if (nintervals < 0) return fail(HAMK_ERR_INVALID, "negative nintervals");
+  if (every < 1) return fail(HAMK_ERR_INVALID, "every must be at least 1 (RK4 steps per renormalisation interval)");
+  if ((int64_t)nintervals * every > 0x7fffffffLL) return fail(HAMK_ERR_INVALID, "nintervals * every does not fit an int32");
+  if (!std::isfinite(dt)) return fail(HAMK_ERR_INVALID, "dt is not finite");
+  if (!std::isfinite(d0) || !(d0 > 0.0)) return fail(HAMK_ERR_INVALID, "d0 must be finite and positive");
+  Variant* v = nullptr;
+  TRY(companion_variant(s, COMPANION_LYAP, &v));
+  if (B == 0 || nintervals == 0) return HAMK_OK;
+  TRY(companion_load(s, v, COMPANION_LYAP));
+  Stager st(s, mem);
+  const size_t cnt = (size_t)s->base.n * B;
+  double *xq, *xp, *xwq, *xwp, *xl; int32_t* dst;
+  TRY(st.inout(q, cnt, &xq));
+  TRY(st.inout(p, cnt, &xp));
+  TRY(st.inout(wq, cnt, &xwq));
+  TRY(st.inout(wp, cnt, &xwp));
+  TRY(st.inout(logsum, (size_t)B, &xl));
+  TRY(st.out(status, (size_t)B, &dst));
+  TRY(launch_lyap(s, B, xq, xp, xwq, xwp, dt, nintervals, every, d0, xl, dst));
   return st.finish();
 }
 

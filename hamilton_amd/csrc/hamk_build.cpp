@@ -40,6 +40,27 @@ static const char kSampleSource[] =
 static const char kSympHeader[] =
 #include "hamk_symp_src.inc"
     ;
+static const char kLyapHeader[] =
+#include "hamk_lyap_src.inc"
+    ;
+
+// What distinguishes the companion modules of the lane variant (hamk_host.h CompanionKind): the header that defines the one
+// kernel, the macro that instantiates it, and what a refusal calls it.
+namespace {
+struct CompanionDesc {
+  const char* header_name;
+  const char* header_src;
+  size_t header_bytes;       // sizeof the embedded text (its terminating NUL included), as the cache key has always fed it
+  const char* instantiate;
+  const char* kernel;
+  const char* what;
+};
+const CompanionDesc kCompanions[COMPANION__COUNT] = {
+    {"hamk_symp.hpp", kSympHeader, sizeof kSympHeader, "HAMK_INSTANTIATE_SYMP", "hamk_symp_steps_k", "the symplectic stepper"},
+    {"hamk_lyap.hpp", kLyapHeader, sizeof kLyapHeader, "HAMK_INSTANTIATE_LYAP", "hamk_lyap_steps_k", "the Lyapunov stepper"},
+};
+}  // namespace
+const char* companion_kernel_name(CompanionKind kind) { return kCompanions[kind].kernel; }
 
 // ---------------------------------------------------------------------------
 // specialisation
@@ -95,7 +116,7 @@ static std::string cache_dir() {
 
 struct CacheKey { std::string path; unsigned char sha[32]; };
 
-static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts, bool cache_on, bool symp) {
+static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts, bool cache_on, CompanionKind companion) {
   CacheKey k;
   std::memset(k.sha, 0, sizeof k.sha);
   const std::string dir = cache_on ? cache_dir() : std::string();
@@ -109,7 +130,7 @@ static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts
   feed(kDeviceHeader, sizeof kDeviceHeader);                // the headers this variant's source includes
   if (s->mapping == HAMK_MAP_WAVE) feed(kWaveHeader, sizeof kWaveHeader);
   if (s->mapping == HAMK_MAP_QUAD) feed(kQuadHeader, sizeof kQuadHeader);
-  if (symp) feed(kSympHeader, sizeof kSympHeader);          // the companion module's source includes it as well
+  if (companion != COMPANION_NONE) feed(kCompanions[companion].header_src, kCompanions[companion].header_bytes);   // a companion module's source includes its header as well
   for (const char* o : opts) feed(o, std::strlen(o) + 1);
   feed(&major, sizeof major);
   feed(&minor, sizeof minor);
@@ -155,11 +176,12 @@ static void cache_store(const CacheKey& k, const std::vector<char>& code) {   //
   if (!out || std::rename(tmp.c_str(), k.path.c_str()) != 0) std::remove(tmp.c_str());
 }
 
-int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, bool symp) {
+int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, CompanionKind companion) {
   hiprtcProgram prog = nullptr;
-  const char* hdr_src[] = {kDeviceHeader, kWaveHeader, kQuadHeader, kSympHeader};
-  const char* hdr_name[] = {"hamk_device.hpp", "hamk_wave.hpp", "hamk_quad.hpp", "hamk_symp.hpp"};
-  hiprtcResult r = hiprtcCreateProgram(&prog, s->source.c_str(), "hamk_system.hip", symp ? 4 : 3, hdr_src, hdr_name);
+  const bool comp = companion != COMPANION_NONE;               // a companion's own header is the fourth of its program, nobody else's
+  const char* hdr_src[] = {kDeviceHeader, kWaveHeader, kQuadHeader, comp ? kCompanions[companion].header_src : nullptr};
+  const char* hdr_name[] = {"hamk_device.hpp", "hamk_wave.hpp", "hamk_quad.hpp", comp ? kCompanions[companion].header_name : nullptr};
+  hiprtcResult r = hiprtcCreateProgram(&prog, s->source.c_str(), "hamk_system.hip", comp ? 4 : 3, hdr_src, hdr_name);
   if (r != HIPRTC_SUCCESS) return fail(HAMK_ERR_COMPILE, std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r));
   std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast",
                                    "-fno-honor-nans", "-fno-signed-zeros"};
@@ -193,7 +215,7 @@ int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<
     }
     for (auto& t : extra_tok) opts.push_back(t.c_str());
   }
-  const CacheKey ckey = cache_key(s, opts, cache_on, symp);
+  const CacheKey ckey = cache_key(s, opts, cache_on, companion);
   if (!ckey.path.empty() && cache_load(ckey, code)) {
     s->build_log = "cache hit: " + ckey.path;
     hiprtcDestroyProgram(&prog);
@@ -345,34 +367,35 @@ size_t chosen_kernel_bytes(const Variant* s, int k) {
   return kernel_code_bytes(s->use2[k] ? s->code2 : s->code, kKernelNames[k]);
 }
 
-// ---- the symplectic stepper's companion module (hamk_symp.hpp) ---------------------------------------------------------
+// ---- the lane variant's companion modules (hamk_symp.hpp, hamk_lyap.hpp) ----------------------------------------------
 // A per-system module holds exactly the nine kernels of HAMK_INSTANTIATE (tests/test_abi.py counts its function symbols and
 // the rows of build_info), and its cache key covers the whole text of hamk_device.hpp: a tenth kernel there would move every
-// existing module.  So hamk_symp_steps_k lives in a module of its own: the lane variant's generated source -- the system's
-// struct and #defines as they are, generate_source is not called again -- with its final HAMK_INSTANTIATE(HamkSys) replaced
-// by the include of hamk_symp.hpp and HAMK_INSTANTIATE_SYMP(HamkSys).  One build with the lane module's option list, through
-// the same on-disk cache; the per-kernel choice between two builds (build_code) is not made here -- DESIGN.md section 11
-// lists what the build without MachineLICM would spill.
-int build_symp(Variant* v, bool cache_on) {
-  if (!v->symp_code.empty()) return HAMK_OK;
+// existing module.  So hamk_symp_steps_k and hamk_lyap_steps_k each live in a module of their own: the lane variant's generated
+// source -- the system's struct and #defines as they are, generate_source is not called again -- with its final
+// HAMK_INSTANTIATE(HamkSys) replaced by the include of the kind's header and its HAMK_INSTANTIATE_*(HamkSys).  One build with the
+// lane module's option list, through the same on-disk cache; the per-kernel choice between two builds (build_code) is not made
+// here -- DESIGN.md sections 11 and 12 list what the kernels spill.
+int build_companion(Variant* v, CompanionKind kind, bool cache_on) {
+  Variant::Companion& c = v->companion[kind];
+  if (!c.code.empty()) return HAMK_OK;
+  const CompanionDesc& k = kCompanions[kind];
   static const char kTail[] = "HAMK_INSTANTIATE(HamkSys)";
   const size_t at = v->source.rfind(kTail);
-  if (v->mapping != HAMK_MAP_LANE || at == std::string::npos) return fail(HAMK_ERR_UNSUPPORTED, "the symplectic stepper needs the one-trajectory-per-lane module");
+  if (v->mapping != HAMK_MAP_LANE || at == std::string::npos) return fail(HAMK_ERR_UNSUPPORTED, std::string(k.what) + " needs the one-trajectory-per-lane module");
   Variant t;
   t.mapping = v->mapping;
   t.desc = v->desc;
-  t.source = v->source.substr(0, at) + "#include \"hamk_symp.hpp\"\nHAMK_INSTANTIATE_SYMP(HamkSys)" + v->source.substr(at + sizeof kTail - 1);
+  t.source = v->source.substr(0, at) + "#include \"" + k.header_name + "\"\n" + k.instantiate + "(HamkSys)" + v->source.substr(at + sizeof kTail - 1);
   std::vector<char> code;
-  TRY(compile_module(&t, cache_on, false, code, true));
-  static const char kName[] = "hamk_symp_steps_k";
+  TRY(compile_module(&t, cache_on, false, code, kind));
   char line[160];
   // functions: the function symbols of the code object -- 1 = every device function was inlined into the one kernel
-  std::snprintf(line, sizeof line, "%s build=default bytes=%zu sgpr_spills=%d vgpr_spills=%d vgprs=%d functions=%zu\n", kName,
-                kernel_code_bytes(code, kName), sgpr_spill_count(code, kName), vgpr_spill_count(code, kName), vgpr_count(code, kName),
+  std::snprintf(line, sizeof line, "%s build=default bytes=%zu sgpr_spills=%d vgpr_spills=%d vgprs=%d functions=%zu\n", k.kernel,
+                kernel_code_bytes(code, k.kernel), sgpr_spill_count(code, k.kernel), vgpr_spill_count(code, k.kernel), vgpr_count(code, k.kernel),
                 kernel_code_bytes(code, nullptr));
-  v->symp_source.swap(t.source);
-  v->symp_info = line;
-  v->symp_code.swap(code);
+  c.source.swap(t.source);
+  c.info = line;
+  c.code.swap(code);
   return HAMK_OK;
 }
 

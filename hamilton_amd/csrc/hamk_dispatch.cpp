@@ -350,7 +350,10 @@ int launch_scribble(hamk_system* s, unsigned seed) {
   return launch_kernel<sig::hamk_scribble_k>::on(s->mod().fn[K_SCRIBBLE], s->cur->stream, 2048 * 256, 256, seed);
 }
 int launch_symp(hamk_system* s, int64_t B, double* q, double* p, int nsteps, int nsub, double ha, double hb, int iters, double* residual, int* status) {
-  return launch_kernel<sig::hamk_symp_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].symp_fn, s->cur->stream, B, 256, q, p, B, nsteps, nsub, ha, hb, iters, residual, status);
+  return launch_kernel<sig::hamk_symp_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].companion_fn[COMPANION_SYMP], s->cur->stream, B, 256, q, p, B, nsteps, nsub, ha, hb, iters, residual, status);
+}
+int launch_lyap(hamk_system* s, int64_t B, double* q, double* p, double* wq, double* wp, double dt, int nintervals, int every, double d0, double* logsum, int* status) {
+  return launch_kernel<sig_lyap::hamk_lyap_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].companion_fn[COMPANION_LYAP], s->cur->stream, B, 256, q, p, wq, wp, B, dt, nintervals, every, d0, logsum, status);
 }
 int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx) {
   return launch_kernel<sig::hamk_sample_k>::on(d->sample_fn, d->stream, B, 256, q, qd, B, first_index, seed, n, bx);

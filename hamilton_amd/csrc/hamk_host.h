@@ -3,7 +3,7 @@
 //   hamk_dispatch.cpp  options -> specialisations (which lanes serve a trajectory, bodies, sincos policy ...), device
 //                      binding, the typed launchers (launch_*), the first-use self-check
 //   hamk_api.cpp       the C ABI of include/hamk.h: argument checks, host-pointer staging, checkpoints
-// and the ONE host-side statement of every kernel's parameter list (namespace sig below): launch_kernel<Sig> builds the argument
+// and the ONE host-side statement of every kernel's parameter list (namespace sig below, sig_lyap beside it): launch_kernel<Sig> builds the argument
 // array from it and is the only caller of hipModuleLaunchKernel; tests/test_kernel_signatures.py holds the table against the
 // device headers.
 #pragma once
@@ -37,6 +37,9 @@ const std::string& last_error_text();
 
 enum KernelId { K_RK4, K_HAMEQS, K_COORDS, K_TO_PHASE, K_FROM_PHASE, K_OBSERVE, K_OBSERVE_CFG, K_RKF45, K_SCRIBBLE, K__COUNT };
 extern const char* const kKernelNames[K__COUNT];
+
+// The lane variant's companion modules: one extra kernel each, in a module of its own (hamk_build.cpp build_companion).
+enum CompanionKind { COMPANION_NONE = -1, COMPANION_SYMP = 0, COMPANION_LYAP = 1, COMPANION__COUNT = 2 };
 
 struct Sha256 {
   uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
@@ -107,11 +110,15 @@ struct Variant {
   int generation = 0;          // bumped whenever `code` is rebuilt (the self-check's recovery path)
   int self_check_rebuilds = 0;
   bool forced_rk4_body = false, forced_rkf_body = false;
-  // the lane variant's COMPANION module (hamk_symp.hpp: hamk_symp_steps_k), built the first time hamk_symplectic_* asks for it;
-  // its own source, code object and one-line description -- no part of `source`, `code`, `build_info` or the kernel counts above
-  std::string symp_source;
-  std::vector<char> symp_code;
-  std::string symp_info;
+  // the lane variant's COMPANION modules, one per kind (hamk_symp.hpp: hamk_symp_steps_k; hamk_lyap.hpp: hamk_lyap_steps_k), each
+  // built the first time its entry points ask for it; its own source, code object and one-line description -- no part of `source`,
+  // `code`, `build_info` or the kernel counts above
+  struct Companion {
+    std::string source;
+    std::vector<char> code;
+    std::string info;
+  };
+  Companion companion[COMPANION__COUNT];      // by CompanionKind
 };
 constexpr int kMaxMap = 4;     // HAMK_MAP_* ids are 1..3
 
@@ -122,12 +129,13 @@ struct DevModule {
   hipFunction_t fn[K__COUNT] = {};
   bool self_checked = false;
   int code_generation = -1;     // Variant::generation the loaded modules were built from
-  hipModule_t symp_module = nullptr;      // the companion module (Variant::symp_code), loaded on first use
-  hipFunction_t symp_fn = nullptr;
+  hipModule_t companion_module[COMPANION__COUNT] = {};      // the companion modules (Variant::companion[kind].code), loaded on first use
+  hipFunction_t companion_fn[COMPANION__COUNT] = {};
   void unload() {
     if (module) { hipModuleUnload(module); module = nullptr; }
     if (module2) { hipModuleUnload(module2); module2 = nullptr; }
-    if (symp_module) { hipModuleUnload(symp_module); symp_module = nullptr; symp_fn = nullptr; }
+    for (int k = 0; k < COMPANION__COUNT; ++k)
+      if (companion_module[k]) { hipModuleUnload(companion_module[k]); companion_module[k] = nullptr; companion_fn[k] = nullptr; }
   }
 };
 
@@ -205,7 +213,7 @@ namespace hamk_host {
 
 // ---- the kernels' signatures -------------------------------------------------------------------------------------------
 // One function type per kernel: the eight of the path (HAMK_INSTANTIATE / _QUAD / _WAVE state the same eight), hamk_scribble_k,
-// the companion module's stepper (hamk_symp.hpp) and the sampler (hamk_sample.hpp).
+// the symplectic companion module's stepper (hamk_symp.hpp) and the sampler (hamk_sample.hpp).
 struct HamkBoxes { double q_lo[64], q_hi[64], qd_lo[64], qd_hi[64]; };      // = hamk_sample.hpp; travels by value
 static_assert(sizeof(HamkBoxes) == 4 * 64 * sizeof(double), "HamkBoxes is hamk_sample_k's last argument, byte for byte");
 namespace sig {
@@ -221,6 +229,11 @@ using hamk_scribble_k = void(unsigned);
 using hamk_symp_steps_k = void(double*, double*, long long, int, int, double, double, int, double*, int*);
 using hamk_sample_k = void(double*, double*, long long, long long, unsigned long long, int, HamkBoxes);
 }  // namespace sig
+// hamk_lyap.hpp's kernel, the Lyapunov companion module's: stated here, beside the table above (tests/test_lyapunov.py holds it
+// against the device header the way tests/test_kernel_signatures.py holds the table)
+namespace sig_lyap {
+using hamk_lyap_steps_k = void(double*, double*, double*, double*, long long, double, int, int, double, double*, int*);
+}  // namespace sig_lyap
 
 // A launch over B trajectories, per_block of them to a block of 256 threads.  The arguments arrive BY VALUE as the signature's own
 // parameter types -- the compiler converts or refuses -- and the argument array is built from them here, nowhere else.
@@ -261,8 +274,9 @@ template <class T> struct DevBuf {
 };
 
 // ---- hamk_build.cpp ---------------------------------------------------------------------------------------------------
-int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, bool symp = false);
-int build_symp(Variant* v, bool cache_on);                 // the lane variant's companion module (hamk_symp.hpp), once
+int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, CompanionKind companion = COMPANION_NONE);
+int build_companion(Variant* v, CompanionKind kind, bool cache_on);     // the lane variant's companion module of that kind, once
+const char* companion_kernel_name(CompanionKind kind);
 int build_code(Variant* s, bool cache_on, int force);      // force: 0 default build only, 1 without MachineLICM only, -1 per kernel
 size_t kernel_code_bytes(const std::vector<char>& elf, const char* name);
 size_t chosen_kernel_bytes(const Variant* s, int k);
@@ -288,7 +302,9 @@ int launch_observe(hamk_system* s, int64_t B, const double* q, const double* p, 
 int launch_observe_config(hamk_system* s, int64_t B, const double* q, const double* qd, double* ke, double* lag);
 int launch_rkf45(hamk_system* s, int64_t B, const RkfCall& c);
 int launch_scribble(hamk_system* s, unsigned seed);         // 2048 blocks, whatever the mapping
-// ... the companion module's stepper (loaded by hamk_symplectic_steps) and the sampler (loaded by hamk_sample_batch): one lane each
+// ... the companion modules' steppers (loaded by hamk_symplectic_steps / hamk_lyapunov_steps) and the sampler (loaded by
+// hamk_sample_batch): one lane each
+int launch_lyap(hamk_system* s, int64_t B, double* q, double* p, double* wq, double* wp, double dt, int nintervals, int every, double d0, double* logsum, int* status);
 int launch_symp(hamk_system* s, int64_t B, double* q, double* p, int nsteps, int nsub, double ha, double hb, int iters, double* residual, int* status);
 int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx);
 

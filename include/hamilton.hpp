@@ -453,6 +453,27 @@ inline Phase symplecticSteps(double dt, int nsteps, System& s, const Phase& ph, 
                               residual ? residual->data() : nullptr, s.last_status.data(), HAMK_MEM_HOST));
   return out;
 }
+// largest-Lyapunov-exponent stepping fused with RK4 (hamk_lyapunov_steps; no reference counterpart; Benettin's two-trajectory
+// method): `nintervals` intervals of `every` RK4 steps of dt, the shadow y + d0 w renormalised after each; n <= 16.  w (a Phase-
+// shaped deviation: positions = wq, momenta = wp) and logsum are advanced in place and carry a run over several calls bit for
+// bit; an EMPTY w / logsum is filled with 1 / sqrt(2n) / zeros first -- a given w is used as it is (a unit vector is the caller's
+// business).  The exponent estimate is logsum / (nintervals every dt).
+inline Phase lyapunovSteps(double dt, int nintervals, int every, System& s, const Phase& ph, Phase& w, std::vector<double>& logsum, double d0 = 1e-7) {
+  Phase out = ph;
+  if (w.positions.empty() && w.momenta.empty()) {
+    w = ph;
+    const double c = 1.0 / std::sqrt(2.0 * (double)ph.n);
+    w.positions.assign(ph.positions.size(), c);
+    w.momenta.assign(ph.momenta.size(), c);
+  }
+  if (logsum.empty()) logsum.assign((size_t)ph.B, 0.0);
+  if (w.positions.size() != ph.positions.size() || w.momenta.size() != ph.momenta.size() || logsum.size() != (size_t)ph.B)
+    throw std::invalid_argument("lyapunovSteps: w and logsum must describe the ensemble of the state");
+  s.last_status.assign((size_t)ph.B, 0);
+  check(hamk_lyapunov_steps(s.handle(), ph.B, out.positions.data(), out.momenta.data(), w.positions.data(), w.momenta.data(), dt, nintervals,
+                            every, d0, logsum.data(), s.last_status.data(), HAMK_MEM_HOST));
+  return out;
+}
 
 // ---------------------------------------------------------------------------------------
 // Ensembles resident in HBM (no reference counterpart: the reference holds one trajectory on the
@@ -528,6 +549,11 @@ inline void rk4Steps(double dt, int nsteps, System& s, DevicePhase& d) {      //
 inline void symplecticSteps(double dt, int nsteps, System& s, DevicePhase& d, int order = 2, int iters = 0) {      // in place, asynchronous
   check(hamk_symplectic_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, order, iters, nullptr,
                               d.status.as<int32_t>(), HAMK_MEM_DEVICE));
+}
+// w: the deviation, Phase-shaped on the device; logsum: B doubles on the device -- both the caller's, initialised by the caller
+inline void lyapunovSteps(double dt, int nintervals, int every, System& s, DevicePhase& d, DevicePhase& w, DeviceArray& logsum, double d0 = 1e-7) {      // in place, asynchronous
+  check(hamk_lyapunov_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), w.positions.as<double>(), w.momenta.as<double>(),
+                            dt, nintervals, every, d0, logsum.as<double>(), d.status.as<int32_t>(), HAMK_MEM_DEVICE));
 }
 inline void stepHam(double r, System& s, DevicePhase& d) {                     // :390-402, in place, asynchronous
   check(hamk_step_ham_batch(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), r, d.status.as<int32_t>(), nullptr, HAMK_MEM_DEVICE));

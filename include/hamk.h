@@ -23,6 +23,7 @@
  *   (no counterpart; named by BASELINE.json north_star) hamk_rk4_steps        (classic fixed-step RK4)
  *   (no counterpart)            hamk_rk4_steps_checked, hamk_checkpoint_*
  *   (no counterpart; a structure-preserving fixed step) hamk_symplectic_steps (implicit midpoint, order 2 / 4)
+ *   (no counterpart; which trajectories are chaotic)    hamk_lyapunov_steps   (largest Lyapunov exponent, fused with RK4)
  *
  * The reference evaluates ONE trajectory per call on the CPU through `ad`
  * (AD), hmatrix (LAPACK/BLAS) and hmatrix-gsl (GSL odeiv).  This library
@@ -360,6 +361,31 @@ int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, doubl
  * needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported for this handle.               */
 const char* hamk_symplectic_source(hamk_system* s);
 const char* hamk_symplectic_build_info(hamk_system* s);
+
+/* Largest-Lyapunov-exponent stepping fused with classic RK4 (Benettin's two-trajectory method), IN PLACE on q, p, wq, wp and
+ * logsum.  Per trajectory: the state y = [q; p], a deviation vector w = [wq; wp] (arrays shaped like q, p) and a running
+ * logsum[B].  One interval: s = y + d0 w; `every` times y <- RK4(y, dt) and s <- RK4(s, dt); then delta = s - y,
+ * d = sqrt(sum_j delta_j^2) over all 2n components, logsum += log(d / d0), w = delta / d.  A call runs `nintervals` intervals in
+ * one launch; the estimate of the largest Lyapunov exponent is logsum / (nintervals every dt), the caller's division.
+ *   w is used EXACTLY AS GIVEN, not normalised at entry: a unit vector (Euclidean norm over all 2n components) is the caller's
+ *   business, and a w of norm c adds log c to the first term of logsum.  logsum is read, added to and written back.  So a run cut
+ *   into calls, w and logsum carried over, reproduces the bits of the one call.  q, p do not depend on w or d0: they are what the
+ *   same RK4 steps alone give.
+ *   q, p, wq, wp, logsum are required; status may be NULL.  status: HAMK_ST_SINGULAR from any right-hand side of either
+ *   trajectory, HAMK_ST_NONFINITE where the final state, w or logsum is not finite (d = 0 gives log 0 and is flagged this way).
+ *   HAMK_ERR_INVALID: a null handle or required array, B < 0, nintervals < 0, every < 1, nintervals * every beyond int32, dt not
+ *   finite, d0 not finite or <= 0, an unknown mem.  One trajectory per lane: n <= 16; HAMK_ERR_UNSUPPORTED for n > 16 or a handle
+ *   whose options state HAMK_MAP_QUAD / HAMK_MAP_WAVE; mapping = HAMK_AUTO ALWAYS runs on the one-trajectory-per-lane module,
+ *   whatever B is.  HAMK_MEM_DEVICE: asynchronous on the handle's stream; HAMK_MEM_HOST: staged, returns with the results in place.
+ *   B == 0 or nintervals == 0: HAMK_OK, nothing launched and nothing written.  The kernel (hamk_lyap.hpp) lives in a companion
+ *   module of the lane module, built the first time one of these three entry points asks for it; the first-use self-check does
+ *   not cover it.  No reference counterpart.                                                                              */
+int hamk_lyapunov_steps(hamk_system* s, int64_t B, double* q, double* p, double* wq, double* wp, double dt,
+                        int32_t nintervals, int32_t every, double d0, double* logsum, int32_t* status, int32_t mem);
+/* Source / one build_info-format line (kernel, bytes, spilled SGPRs and VGPRs, allocated VGPRs, function symbols) of that
+ * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
+const char* hamk_lyapunov_source(hamk_system* s);
+const char* hamk_lyapunov_build_info(hamk_system* s);
 
 /* stepHam dt: adaptive RKF45 with GSL's standard controller from 0 to dt,
  * h0 = dt/100, eps_abs = eps_rel = 1.49012e-08, IN PLACE.  Hamilton.hs:390-402,

@@ -91,6 +91,9 @@ def jobs():
     for n in ("pendulum", "doublePendulum", "opcodeZoo", "room", "twoBody", "chain8", "chain16", "doublePendulum~mixed"):
         out.append((f"symp_{n}", {}, False))
     out.append(("symp_doublePendulum", {"HAMK_K_SYMBOLIC": "0"}, False))
+    # the Lyapunov stepper's companion module (hamk_lyap.hpp) of the systems tests/test_gpu_lyapunov.py steps, its two anchors included
+    for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "anchor_saddle", "anchor_oscillator"):
+        out.append((f"lyap_{n}", {}, False))
     return rect + out
 
 
@@ -128,6 +131,12 @@ def build(job):
         elif name.startswith("symp_"):
             s = api.system_from_spec(examples.get(name[5:]))
             return name, env, s.symplectic_build_info.strip()
+        elif name.startswith("lyap_anchor_"):
+            import test_lyapunov
+            return name, env, test_lyapunov.anchor_system(name[12:]).lyapunov_build_info.strip()
+        elif name.startswith("lyap_"):
+            s = api.system_from_spec(examples.get(name[5:]))
+            return name, env, s.lyapunov_build_info.strip()
         elif name.startswith("rewrite_"):
             import rewrite_family
             key, variant = name[8:].split("@")
