@@ -48,6 +48,8 @@ module Numeric.Hamilton.HIP
   , rk4StepsBatch
   , symplecticStepsBatch
   , lyapunovStepsBatch
+  , SectionHits(..)
+  , poincareStepsBatch
   , evolveHamEnsemble
     -- * ensembles resident in HBM, several GPUs from one process
   , DeviceEnsemble
@@ -213,6 +215,9 @@ foreign import ccall safe "hamk_symplectic_steps"
 foreign import ccall safe "hamk_lyapunov_steps"
   c_lyapunov_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32
                    -> Double -> Ptr Double -> Ptr Int32 -> Int32 -> IO CInt
+foreign import ccall safe "hamk_poincare_steps"
+  c_poincare_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32 -> Double -> Double -> Int32 -> Int32
+                   -> Ptr Double -> Ptr Double -> Ptr Double -> Ptr Int32 -> Int64 -> Ptr Int32 -> Int32 -> IO CInt
 foreign import ccall safe "hamk_checkpoint_write"
   c_ck_write :: CString -> Int32 -> Int64 -> Ptr Double -> Ptr Double -> Int32 -> Int64 -> Word64 -> Double -> IO CInt
 foreign import ccall safe "hamk_checkpoint_info"
@@ -528,6 +533,39 @@ lyapunovStepsBatch dt k every d0 (HipSystem h) e w logsum = withForeignPtr h $ \
       "lyapunovSteps"
   w' <- Ensemble (ensSize w) <$> VS.unsafeFreeze wq <*> VS.unsafeFreeze wp
   (,,) e' w' <$> VS.unsafeFreeze ls
+
+-- | What 'poincareStepsBatch' recorded: the states at the crossings (@[maxHits][n][B]@ each), their times in units of @dt@
+--   (@[maxHits][B]@) and per trajectory the crossings seen -- which may exceed @maxHits@; rows at or beyond the count hold nothing.
+data SectionHits = SectionHits
+  { hitMax :: !Int
+  , hitPositions :: !(VS.Vector Double)
+  , hitMomenta :: !(VS.Vector Double)
+  , hitTimes :: !(VS.Vector Double)
+  , hitCount :: !(VS.Vector Int32)
+  }
+
+-- | Poincare sections fused with RK4 (no counterpart in the reference): @k@ RK4 steps of @dt@, and the crossings of component
+--   @coord@ of @[q; p]@ through @y = level@ (@period@ 0) or @y = level (mod period)@, located inside the step on RK4's cubic
+--   continuous extension.  @direction@: 1 upward, -1 downward, 0 both; at most one crossing per step.  @Left maxHits@ starts from
+--   zeroed buffers; @Right hits@ with @step0@ = the steps taken so far continues a run bit for bit.  One trajectory per lane:
+--   @n <= 16@.
+poincareStepsBatch :: forall m n. KnownNat n => Double -> Int -> Int -> Double -> Double -> Int -> Either Int SectionHits -> Int64
+                   -> HipSystem m n -> Ensemble n -> IO (Ensemble n, SectionHits)
+poincareStepsBatch dt k coord level period direction start step0 (HipSystem h) e = withForeignPtr h $ \s -> do
+  let rows = either id hitMax start
+      nb = ensSize e
+      nq = VS.length (ensPositions e)
+      begin f z = either (const (pure z)) (pure . f) start
+  hq <- VS.thaw =<< begin hitPositions (VS.replicate (rows * nq) 0)
+  hp <- VS.thaw =<< begin hitMomenta (VS.replicate (rows * nq) 0)
+  ht <- VS.thaw =<< begin hitTimes (VS.replicate (rows * nb) 0)
+  hn <- VS.thaw =<< begin hitCount (VS.replicate nb 0)
+  e' <- VSM.unsafeWith hq $ \phq -> VSM.unsafeWith hp $ \php -> VSM.unsafeWith ht $ \pht -> VSM.unsafeWith hn $ \phn ->
+    inPlace e (\b pq pp -> c_poincare_steps s b pq pp dt (fromIntegral k) (fromIntegral coord) level period (fromIntegral direction)
+                             (fromIntegral rows) phq php pht phn step0 nullPtr memHost)
+      "poincareSteps"
+  hits <- SectionHits rows <$> VS.unsafeFreeze hq <*> VS.unsafeFreeze hp <*> VS.unsafeFreeze ht <*> VS.unsafeFreeze hn
+  pure (e', hits)
 
 -- | 'evolveHam' (Hamilton.hs:433-462) for every member: one ensemble per requested time,
 --   element 0 being the initial ensemble.

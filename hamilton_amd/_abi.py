@@ -104,6 +104,9 @@ SIGNATURES = {
     "hamk_lyapunov_steps": (ctypes.c_int, [_h, _i64, _dp, _dp, _dp, _dp, _f64, _i32, _i32, _f64, _dp, _ip, _i32]),
     "hamk_lyapunov_source": (ctypes.c_char_p, [_h]),
     "hamk_lyapunov_build_info": (ctypes.c_char_p, [_h]),
+    "hamk_poincare_steps": (ctypes.c_int, [_h, _i64, _dp, _dp, _f64, _i32, _i32, _f64, _f64, _i32, _i32, _dp, _dp, _dp, _ip, _i64, _ip, _i32]),
+    "hamk_poincare_source": (ctypes.c_char_p, [_h]),
+    "hamk_poincare_build_info": (ctypes.c_char_p, [_h]),
     "hamk_system_set_gsl_api": (ctypes.c_int, [_h, _i32]),
     "hamk_system_get_gsl_api": (_i32, [_h]),
     "hamk_system_code_object": (_i64, [_h, _i32, ctypes.c_void_p, _i64]),

@@ -241,7 +241,7 @@ class System:
         text = fn(self._h)
         if text is None:
             msg = _abi.lib().hamk_last_error().decode("utf-8", "replace")
-            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper")) or "unsupported" in msg
+            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper", "the Poincare-section stepper")) or "unsupported" in msg
             raise HamkError(_abi.HAMK_ERR_UNSUPPORTED if unsupported else _abi.HAMK_ERR_COMPILE, msg)
         return text.decode()
 
@@ -264,6 +264,16 @@ class System:
     def lyapunov_build_info(self) -> str:
         """One `build_info`-format line for hamk_lyap_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
         return self._symplectic_text(_abi.lib().hamk_lyapunov_build_info)
+
+    @property
+    def poincare_source(self) -> str:
+        """Source of the Poincare-section stepper's companion module (hamk_poincare_source; builds it if needed, needs no GPU)."""
+        return self._symplectic_text(_abi.lib().hamk_poincare_source)
+
+    @property
+    def poincare_build_info(self) -> str:
+        """One `build_info`-format line for hamk_psec_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
+        return self._symplectic_text(_abi.lib().hamk_poincare_build_info)
 
     def kernel_bytes(self, kernel: str) -> int:
         return int(_abi.lib().hamk_system_kernel_bytes(self._h, kernel.encode()))
@@ -631,6 +641,75 @@ def lyapunovSteps(dt: float, nintervals: int, every: int, s: System, ph: Phase, 
     s._after(st, qa.single, "lyapunovSteps")
     return (Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Phase(_shape_out(wq, qa.single), _shape_out(wp, qa.single)),
             _shape_out(ls, qa.single))
+
+
+class Hits:
+    """What poincareSteps recorded: `positions`, `momenta` [max_hits, n, B] (row r: the state at a trajectory's r-th crossing),
+    `times` [max_hits, B] (in units of dt: steps taken + the fraction of the crossing step) and `count` [B] (int32; crossings seen,
+    which may exceed max_hits -- rows at or beyond min(count, max_hits) hold nothing).  For one trajectory the B axis is dropped."""
+
+    def __init__(self, positions, momenta, times, count):
+        self.positions = positions
+        self.momenta = momenta
+        self.times = times
+        self.count = count
+
+    def __repr__(self):
+        return f"Hits {{count = {self.count!r}, max_hits = {self.positions.shape[0]}}}"
+
+
+def poincareSteps(dt: float, nsteps: int, s: System, ph: Phase, coord: int, level: float = 0.0, period: float = 0.0, direction: int = 1,
+                  max_hits: int = 16, hits: Optional[Hits] = None, step0: int = 0, inplace: bool = False):
+    """Poincare sections fused with RK4 (hamk_poincare_steps; no reference counterpart): `nsteps` RK4 steps of `dt`, and the
+    crossings of component `coord` of [q; p] (coord < n: positions, else momenta) through y = level (period = 0) or
+    y = level mod period, located inside the step on RK4's cubic continuous extension and recorded inside the launch.
+    direction: +1 upward crossings, -1 downward, 0 both; at most one per step.  Returns (Phase, Hits).  hits=None: zeroed buffers
+    of `max_hits` rows; passing the returned Hits back with step0 = the steps taken so far continues the run bit for bit (its row
+    count then replaces max_hits).  Hits.count keeps counting beyond the rows there are.  inplace=True advances the given arrays
+    (state, and the hit buffers where given) without copying.  One trajectory per lane: n <= 16."""
+    qa, pa = _pair(ph.positions, "positions", ph.momenta, "momenta", s.n)
+    if inplace:
+        _in_place(qa, ph.positions, "positions"); _in_place(pa, ph.momenta, "momenta")
+    q, p = (qa.a, pa.a) if inplace else (qa.clone(), pa.clone())
+    if hits is None:
+        rows = int(max_hits)
+        if rows < 1:
+            raise ValueError("max_hits must be at least 1")
+        hq, hp = qa.like(s.n, lead=(rows,), zero=True), qa.like(s.n, lead=(rows,), zero=True)
+        ht, hn = qa.like(None, lead=(rows,), zero=True), qa.like(None, "i4", zero=True)
+    else:
+        rows = int(hits.positions.shape[0])
+        bufs = []
+        for a, shape, name, f8 in ((hits.positions, (rows, s.n, qa.B), "hits.positions", True), (hits.momenta, (rows, s.n, qa.B), "hits.momenta", True),
+                                   (hits.times, (rows, qa.B), "hits.times", True), (hits.count, (qa.B,), "hits.count", False)):
+            if _is_torch(a) != qa.device or (qa.device and a.device != qa.a.device):
+                raise ValueError(f"{name} must live in the memory of the state")
+            if not qa.device:
+                a = np.asarray(a)
+            want = torch.float64 if (f8 and qa.device) else torch.int32 if qa.device else np.float64 if f8 else np.int32
+            if a.dtype != want or int(np.prod(a.shape)) != int(np.prod(shape)):
+                raise ValueError(f"{name}: expected {'float64' if f8 else 'int32'} of shape {shape}")
+            b = a.reshape(shape)
+            if qa.device:
+                b = b.contiguous()
+                same = b.data_ptr() == a.data_ptr()
+                b = b if inplace else b.clone()
+            else:
+                b = np.ascontiguousarray(b)
+                same = b.ctypes.data == a.ctypes.data
+                b = b if inplace else b.copy()
+            if inplace and not same:
+                raise ValueError(f"inplace=True needs {name} contiguous")
+            bufs.append(b)
+        hq, hp, ht, hn = bufs
+    # zeroed: with nothing to do (nsteps = 0, an empty ensemble) the call returns HAMK_OK without writing status
+    st = qa.like(None, "i4", zero=True)
+    with s._on(qa):
+        _abi.check(_abi.lib().hamk_poincare_steps(s._h, qa.B, _ptr(q), _ptr(p), float(dt), int(nsteps), int(coord), float(level), float(period),
+                                                  int(direction), rows, _ptr(hq), _ptr(hp), _ptr(ht), _ptr(hn), int(step0), _ptr(st), qa.mem))
+    s._after(st, qa.single, "poincareSteps")
+    drop = (lambda x: x[..., 0]) if qa.single else (lambda x: x)
+    return Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Hits(drop(hq), drop(hp), drop(ht), drop(hn))
 
 
 # ---------------------------------------------------------------------------------------

@@ -707,11 +707,12 @@ int hamk_rk4_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, i
   return hamk_rk4_steps_checked(s, B, q, p, dt, nsteps, 0.0, status, mem);
 }
 
-// ---- the lane variant's companion modules: symplectic stepping (hamk_symp.hpp), Lyapunov stepping (hamk_lyap.hpp) --------
+// ---- the lane variant's companion modules: symplectic stepping (hamk_symp.hpp), Lyapunov stepping (hamk_lyap.hpp), ------
+// ---- Poincare sections (hamk_psec.hpp)
 // The lane variant of a handle that can run a companion's stepper, that companion module built: n <= 16 and no other mapping
 // stated.  AUTO never leaves the lane mapping here, whatever B is (its small-ensemble rule for 11 <= n <= 16 was measured on RK4).
 static int companion_variant(hamk_system* s, CompanionKind kind, Variant** out) {
-  const std::string what = kind == COMPANION_SYMP ? "the symplectic stepper" : "the Lyapunov stepper";
+  const std::string what = companion_what(kind);
   if (s->base.n > 16)
     return fail(HAMK_ERR_UNSUPPORTED, what + " runs one trajectory per lane: n <= 16 (this system has n = " + std::to_string(s->base.n) + ")");
   if (s->opt.mapping == HAMK_MAP_QUAD || s->opt.mapping == HAMK_MAP_WAVE)
@@ -744,6 +745,8 @@ const char* hamk_symplectic_source(hamk_system* s) { return companion_text(s, CO
 const char* hamk_symplectic_build_info(hamk_system* s) { return companion_text(s, COMPANION_SYMP, true); }
 const char* hamk_lyapunov_source(hamk_system* s) { return companion_text(s, COMPANION_LYAP, false); }
 const char* hamk_lyapunov_build_info(hamk_system* s) { return companion_text(s, COMPANION_LYAP, true); }
+const char* hamk_poincare_source(hamk_system* s) { return companion_text(s, COMPANION_PSEC, false); }
+const char* hamk_poincare_build_info(hamk_system* s) { return companion_text(s, COMPANION_PSEC, true); }
 
 int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t order,
                           int32_t iters, double* residual, int32_t* status, int32_t mem) {
@@ -794,6 +797,43 @@ int hamk_lyapunov_steps(hamk_system* s, int64_t B, double* q, double* p, double*
   TRY(st.inout(logsum, (size_t)B, &xl));
   TRY(st.out(status, (size_t)B, &dst));
   TRY(launch_lyap(s, B, xq, xp, xwq, xwp, dt, nintervals, every, d0, xl, dst));
+  return st.finish();
+}
+
+int hamk_poincare_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t coord, double level,
+                        double period, int32_t direction, int32_t max_hits, double* qhit, double* phit, double* thit, int32_t* nhit,
+                        int64_t step0, int32_t* status, int32_t mem) {
+  TRY(check_call(s, B, mem));
+  if (!q || !p || !qhit || !phit || !nhit) return fail(HAMK_ERR_INVALID, "null q / p / qhit / phit / nhit");
+  if (nsteps < 0) return fail(HAMK_ERR_INVALID, "negative nsteps");
+  const int64_t n = s->base.n;
+  if (coord < 0 || coord >= 2 * n) return fail(HAMK_ERR_INVALID, "coord must be 0 .. 2n - 1 (q[coord], or p[coord - n]); this system has n = " + std::to_string(n));
+  if (!std::isfinite(dt)) return fail(HAMK_ERR_INVALID, "dt is not finite");
+  if (!std::isfinite(level)) return fail(HAMK_ERR_INVALID, "level is not finite");
+  if (!std::isfinite(period) || period < 0.0) return fail(HAMK_ERR_INVALID, "period must be finite and >= 0 (0: the plane y[coord] = level)");
+  if (direction < -1 || direction > 1) return fail(HAMK_ERR_INVALID, "direction must be +1 (upward), -1 (downward) or 0 (both)");
+  if (max_hits < 1) return fail(HAMK_ERR_INVALID, "max_hits must be at least 1");
+  // the hit buffers hold max_hits n B doubles each: at most 2^48 of them, so that their byte count and the kernel's 64-bit index stay
+  // far inside an int64 (max_hits n <= 2^31 * 16 cannot overflow before the division)
+  if (B > 0 && (int64_t)max_hits * n > (INT64_C(1) << 48) / B) return fail(HAMK_ERR_INVALID, "max_hits * n * B exceeds 2^48 elements");
+  if (step0 < 0) return fail(HAMK_ERR_INVALID, "negative step0");
+  if (step0 > (INT64_C(1) << 52)) return fail(HAMK_ERR_INVALID, "step0 exceeds 2^52: step0 + step index would not be exact as a double");
+  Variant* v = nullptr;
+  TRY(companion_variant(s, COMPANION_PSEC, &v));
+  if (B == 0 || nsteps == 0) return HAMK_OK;
+  TRY(companion_load(s, v, COMPANION_PSEC));
+  Stager st(s, mem);
+  const size_t cnt = (size_t)n * B, hits = (size_t)max_hits * cnt;
+  double *xq, *xp; int32_t* dst;
+  PsecCall c{dt, nsteps, coord, level, period, direction, max_hits, nullptr, nullptr, nullptr, nullptr, step0};
+  TRY(st.inout(q, cnt, &xq));
+  TRY(st.inout(p, cnt, &xp));
+  TRY(st.inout(qhit, hits, &c.qhit));              // inout: rows at or beyond the count are never written and must survive the staging
+  TRY(st.inout(phit, hits, &c.phit));
+  TRY(st.inout(thit, (size_t)max_hits * B, &c.thit));
+  TRY(st.inout(nhit, (size_t)B, &c.nhit));
+  TRY(st.out(status, (size_t)B, &dst));
+  TRY(launch_psec(s, B, xq, xp, c, dst));
   return st.finish();
 }
 

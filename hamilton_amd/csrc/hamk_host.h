@@ -3,7 +3,7 @@
 //   hamk_dispatch.cpp  options -> specialisations (which lanes serve a trajectory, bodies, sincos policy ...), device
 //                      binding, the typed launchers (launch_*), the first-use self-check
 //   hamk_api.cpp       the C ABI of include/hamk.h: argument checks, host-pointer staging, checkpoints
-// and the ONE host-side statement of every kernel's parameter list (namespace sig below, sig_lyap beside it): launch_kernel<Sig> builds the argument
+// and the ONE host-side statement of every kernel's parameter list (namespace sig below, sig_lyap and sig_psec beside it): launch_kernel<Sig> builds the argument
 // array from it and is the only caller of hipModuleLaunchKernel; tests/test_kernel_signatures.py holds the table against the
 // device headers.
 #pragma once
@@ -39,7 +39,7 @@ enum KernelId { K_RK4, K_HAMEQS, K_COORDS, K_TO_PHASE, K_FROM_PHASE, K_OBSERVE, 
 extern const char* const kKernelNames[K__COUNT];
 
 // The lane variant's companion modules: one extra kernel each, in a module of its own (hamk_build.cpp build_companion).
-enum CompanionKind { COMPANION_NONE = -1, COMPANION_SYMP = 0, COMPANION_LYAP = 1, COMPANION__COUNT = 2 };
+enum CompanionKind { COMPANION_NONE = -1, COMPANION_SYMP = 0, COMPANION_LYAP = 1, COMPANION_PSEC = 2, COMPANION__COUNT = 3 };
 
 struct Sha256 {
   uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
@@ -110,7 +110,8 @@ struct Variant {
   int generation = 0;          // bumped whenever `code` is rebuilt (the self-check's recovery path)
   int self_check_rebuilds = 0;
   bool forced_rk4_body = false, forced_rkf_body = false;
-  // the lane variant's COMPANION modules, one per kind (hamk_symp.hpp: hamk_symp_steps_k; hamk_lyap.hpp: hamk_lyap_steps_k), each
+  // the lane variant's COMPANION modules, one per kind (hamk_symp.hpp: hamk_symp_steps_k; hamk_lyap.hpp: hamk_lyap_steps_k;
+  // hamk_psec.hpp: hamk_psec_steps_k), each
   // built the first time its entry points ask for it; its own source, code object and one-line description -- no part of `source`,
   // `code`, `build_info` or the kernel counts above
   struct Companion {
@@ -234,6 +235,10 @@ using hamk_sample_k = void(double*, double*, long long, long long, unsigned long
 namespace sig_lyap {
 using hamk_lyap_steps_k = void(double*, double*, double*, double*, long long, double, int, int, double, double*, int*);
 }  // namespace sig_lyap
+// hamk_psec.hpp's kernel, the Poincare-section companion module's (tests/test_poincare.py holds it against the device header)
+namespace sig_psec {
+using hamk_psec_steps_k = void(double*, double*, long long, double, int, int, double, double, int, int, double*, double*, double*, int*, long long, int*);
+}  // namespace sig_psec
 
 // A launch over B trajectories, per_block of them to a block of 256 threads.  The arguments arrive BY VALUE as the signature's own
 // parameter types -- the compiler converts or refuses -- and the argument array is built from them here, nowhere else.
@@ -277,6 +282,7 @@ template <class T> struct DevBuf {
 int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, CompanionKind companion = COMPANION_NONE);
 int build_companion(Variant* v, CompanionKind kind, bool cache_on);     // the lane variant's companion module of that kind, once
 const char* companion_kernel_name(CompanionKind kind);
+const char* companion_what(CompanionKind kind);                     // what a refusal calls the kind's stepper
 int build_code(Variant* s, bool cache_on, int force);      // force: 0 default build only, 1 without MachineLICM only, -1 per kernel
 size_t kernel_code_bytes(const std::vector<char>& elf, const char* name);
 size_t chosen_kernel_bytes(const Variant* s, int k);
@@ -302,9 +308,14 @@ int launch_observe(hamk_system* s, int64_t B, const double* q, const double* p, 
 int launch_observe_config(hamk_system* s, int64_t B, const double* q, const double* qd, double* ke, double* lag);
 int launch_rkf45(hamk_system* s, int64_t B, const RkfCall& c);
 int launch_scribble(hamk_system* s, unsigned seed);         // 2048 blocks, whatever the mapping
-// ... the companion modules' steppers (loaded by hamk_symplectic_steps / hamk_lyapunov_steps) and the sampler (loaded by
+// ... the companion modules' steppers (loaded by hamk_symplectic_steps / hamk_lyapunov_steps / hamk_poincare_steps) and the sampler (loaded by
 // hamk_sample_batch): one lane each
 int launch_lyap(hamk_system* s, int64_t B, double* q, double* p, double* wq, double* wp, double dt, int nintervals, int every, double d0, double* logsum, int* status);
+struct PsecCall {             // hamk_psec_steps_k's arguments after (q, p, B), as hamk_poincare_steps checked them
+  double dt; int nsteps; int coord; double level, period; int direction, max_hits;
+  double *qhit, *phit, *thit; int* nhit; long long step0;
+};
+int launch_psec(hamk_system* s, int64_t B, double* q, double* p, const PsecCall& c, int* status);
 int launch_symp(hamk_system* s, int64_t B, double* q, double* p, int nsteps, int nsub, double ha, double hb, int iters, double* residual, int* status);
 int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx);
 

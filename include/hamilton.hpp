@@ -474,6 +474,34 @@ inline Phase lyapunovSteps(double dt, int nintervals, int every, System& s, cons
                             every, d0, logsum.data(), s.last_status.data(), HAMK_MEM_HOST));
   return out;
 }
+// Poincare sections fused with RK4 (hamk_poincare_steps; no reference counterpart): the crossings of component `coord` of [q; p]
+// through y = level (period 0) or y = level mod period, located inside the step on RK4's cubic continuous extension; n <= 16.
+// positions / momenta: [max_hits][n][B]; times: [max_hits][B], in units of dt; count: [B], crossings seen -- it may exceed
+// max_hits, rows at or beyond it hold nothing.  An EMPTY Hits is sized to max_hits zeroed rows first; feeding the same Hits to the
+// next call with step0 = the steps taken so far continues the run bit for bit.
+struct Hits {
+  int max_hits = 16;
+  std::vector<double> positions, momenta, times;
+  std::vector<int32_t> count;
+};
+inline Phase poincareSteps(double dt, int nsteps, System& s, const Phase& ph, int coord, Hits& hits, double level = 0.0, double period = 0.0,
+                           int direction = 1, int64_t step0 = 0) {
+  Phase out = ph;
+  const size_t rows = (size_t)(hits.max_hits > 0 ? hits.max_hits : 0), nb = (size_t)ph.B;
+  if (hits.positions.empty() && hits.momenta.empty() && hits.times.empty() && hits.count.empty()) {
+    hits.positions.assign(rows * ph.positions.size(), 0.0);
+    hits.momenta.assign(rows * ph.momenta.size(), 0.0);
+    hits.times.assign(rows * nb, 0.0);
+    hits.count.assign(nb, 0);
+  }
+  if (hits.positions.size() != rows * ph.positions.size() || hits.momenta.size() != rows * ph.momenta.size() || hits.times.size() != rows * nb ||
+      hits.count.size() != nb)
+    throw std::invalid_argument("poincareSteps: hits must hold max_hits rows of the ensemble of the state");
+  s.last_status.assign(nb, 0);
+  check(hamk_poincare_steps(s.handle(), ph.B, out.positions.data(), out.momenta.data(), dt, nsteps, coord, level, period, direction, hits.max_hits,
+                            hits.positions.data(), hits.momenta.data(), hits.times.data(), hits.count.data(), step0, s.last_status.data(), HAMK_MEM_HOST));
+  return out;
+}
 
 // ---------------------------------------------------------------------------------------
 // Ensembles resident in HBM (no reference counterpart: the reference holds one trajectory on the
@@ -554,6 +582,13 @@ inline void symplecticSteps(double dt, int nsteps, System& s, DevicePhase& d, in
 inline void lyapunovSteps(double dt, int nintervals, int every, System& s, DevicePhase& d, DevicePhase& w, DeviceArray& logsum, double d0 = 1e-7) {      // in place, asynchronous
   check(hamk_lyapunov_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), w.positions.as<double>(), w.momenta.as<double>(),
                             dt, nintervals, every, d0, logsum.as<double>(), d.status.as<int32_t>(), HAMK_MEM_DEVICE));
+}
+// qhit, phit: max_hits n B doubles, thit: max_hits B doubles (may be an empty DeviceArray's null), nhit: B int32 -- all on the
+// device, the caller's, initialised by the caller (nhit = 0 for a new run)
+inline void poincareSteps(double dt, int nsteps, System& s, DevicePhase& d, int coord, double level, double period, int direction, int max_hits,
+                          DeviceArray& qhit, DeviceArray& phit, DeviceArray& thit, DeviceArray& nhit, int64_t step0 = 0) {      // in place, asynchronous
+  check(hamk_poincare_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, coord, level, period, direction, max_hits,
+                            qhit.as<double>(), phit.as<double>(), thit.as<double>(), nhit.as<int32_t>(), step0, d.status.as<int32_t>(), HAMK_MEM_DEVICE));
 }
 inline void stepHam(double r, System& s, DevicePhase& d) {                     // :390-402, in place, asynchronous
   check(hamk_step_ham_batch(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), r, d.status.as<int32_t>(), nullptr, HAMK_MEM_DEVICE));

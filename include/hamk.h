@@ -24,6 +24,7 @@
  *   (no counterpart)            hamk_rk4_steps_checked, hamk_checkpoint_*
  *   (no counterpart; a structure-preserving fixed step) hamk_symplectic_steps (implicit midpoint, order 2 / 4)
  *   (no counterpart; which trajectories are chaotic)    hamk_lyapunov_steps   (largest Lyapunov exponent, fused with RK4)
+ *   (no counterpart; the surface of section)            hamk_poincare_steps   (crossings recorded inside a fused RK4 launch)
  *
  * The reference evaluates ONE trajectory per call on the CPU through `ad`
  * (AD), hmatrix (LAPACK/BLAS) and hmatrix-gsl (GSL odeiv).  This library
@@ -386,6 +387,46 @@ int hamk_lyapunov_steps(hamk_system* s, int64_t B, double* q, double* p, double*
  * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
 const char* hamk_lyapunov_source(hamk_system* s);
 const char* hamk_lyapunov_build_info(hamk_system* s);
+
+/* Poincare sections fused with classic RK4: `nsteps` RK4 steps of dt IN PLACE on q, p (the right-hand side and the step of
+ * hamk_lyapunov_steps, one trajectory per lane), and after every step the crossing of ONE component of y = [q; p] through a
+ * surface, located inside the step and recorded inside the launch.
+ *   The surface.  coord in [0, 2n): yc = q[coord] for coord < n, p[coord - n] otherwise.  period == 0: the plane yc = level.
+ *   period > 0: the family yc = level (mod period) -- angles need it: a pendulum that flips over winds its angle past 2 pi.
+ *   The cell index c(y) = floor((yc - level) / period) for period > 0, (yc >= level ? 0 : -1) for period == 0, a double.
+ *   A step from y0 to y1 crosses UPWARD where c(y1) > c(y0), the target value being level + c(y1) period, and DOWNWARD where
+ *   c(y1) < c(y0), target level + c(y0) period.  direction: +1 counts upward crossings only, -1 downward only, 0 both; "upward" is
+ *   in stepping order, whatever the sign of dt.  AT MOST ONE crossing is recorded per step: dt is expected to resolve the motion
+ *   (a step that passes several members of the family, or leaves and re-enters a cell, records one crossing or none).  A step
+ *   with a non-finite yc at either end (a NaN compares false) records nothing.
+ *   Where inside the step: theta in [0, 1] with Yc(theta) = target on RK4's own third-order continuous extension
+ *       Y(theta) = y0 + dt [b1 k1 + b2 (k2 + k3) + b4 k4],  b1 = theta - 3 theta^2 / 2 + 2 theta^3 / 3,  b2 = theta^2 - 2 theta^3 / 3,
+ *       b4 = -theta^2 / 2 + 2 theta^3 / 3   (Y(1) is the RK4 step; no extra right-hand side, nothing carried between steps),
+ *   from the secant value (target - y0c) / (y1c - y0c) by FOUR Newton iterations, theta clamped to [0, 1] after each, a non-finite
+ *   update leaving theta as it was.  The hit is Y(theta) in all 2n components; the section component is stored as computed, not
+ *   snapped to the target.
+ *   Outputs.  qhit, phit: [max_hits][n][B]; thit: [max_hits][B], may be NULL; nhit: [B].  nhit is READ, ADDED TO AND WRITTEN BACK:
+ *   a crossing goes to row nhit[i] if that row exists (0 <= nhit[i] < max_hits) and is counted either way, so nhit > max_hits is how
+ *   a caller learns of an overflow; rows at or beyond the count are never written.  thit = (double)(step0 + step index) + theta, in
+ *   units of dt, step0 being the caller's count of steps already taken.  So N steps in one call equal N1 + N2 in two calls with
+ *   step0 = N1 and the buffers carried over, bit for bit on every output; and q, p do not depend on the surface arguments.
+ *   q, p, qhit, phit, nhit are required; thit and status may be NULL.  status: HAMK_ST_SINGULAR from any right-hand side,
+ *   HAMK_ST_NONFINITE where the final state is not finite.
+ *   HAMK_ERR_INVALID: a null handle or required array, B < 0, nsteps < 0, coord outside [0, 2n), dt or level not finite, period
+ *   negative or not finite, direction outside {-1, 0, 1}, max_hits < 1, max_hits * n * B beyond 2^48 elements, step0 < 0 or beyond
+ *   2^52, an unknown mem.  One trajectory per lane: n <= 16; HAMK_ERR_UNSUPPORTED for n > 16 or a handle whose options state
+ *   HAMK_MAP_QUAD / HAMK_MAP_WAVE; mapping = HAMK_AUTO ALWAYS runs on the one-trajectory-per-lane module, whatever B is.
+ *   HAMK_MEM_DEVICE: asynchronous on the handle's stream; HAMK_MEM_HOST: staged (the hit buffers and nhit both ways), returns with
+ *   the results in place.  B == 0 or nsteps == 0: HAMK_OK, nothing launched and nothing written.  The kernel (hamk_psec.hpp) lives
+ *   in a companion module of the lane module, built the first time one of these three entry points asks for it; the first-use
+ *   self-check does not cover it.  No reference counterpart.                                                              */
+int hamk_poincare_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t coord, double level,
+                        double period, int32_t direction, int32_t max_hits, double* qhit, double* phit, double* thit,
+                        int32_t* nhit, int64_t step0, int32_t* status, int32_t mem);
+/* Source / one build_info-format line (kernel, bytes, spilled SGPRs and VGPRs, allocated VGPRs, function symbols) of that
+ * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
+const char* hamk_poincare_source(hamk_system* s);
+const char* hamk_poincare_build_info(hamk_system* s);
 
 /* stepHam dt: adaptive RKF45 with GSL's standard controller from 0 to dt,
  * h0 = dt/100, eps_abs = eps_rel = 1.49012e-08, IN PLACE.  Hamilton.hs:390-402,

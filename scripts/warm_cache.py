@@ -94,6 +94,9 @@ def jobs():
     # the Lyapunov stepper's companion module (hamk_lyap.hpp) of the systems tests/test_gpu_lyapunov.py steps, its two anchors included
     for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "anchor_saddle", "anchor_oscillator"):
         out.append((f"lyap_{n}", {}, False))
+    # the Poincare-section stepper's companion module (hamk_psec.hpp) of the systems tests/test_gpu_poincare.py steps, its two anchors included
+    for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "anchor_rotor", "anchor_oscillator"):
+        out.append((f"psec_{n}", {}, False))
     return rect + out
 
 
@@ -134,6 +137,12 @@ def build(job):
         elif name.startswith("lyap_anchor_"):
             import test_lyapunov
             return name, env, test_lyapunov.anchor_system(name[12:]).lyapunov_build_info.strip()
+        elif name.startswith("psec_anchor_"):
+            import test_poincare
+            return name, env, test_poincare.anchor_system(name[12:]).poincare_build_info.strip()
+        elif name.startswith("psec_"):
+            s = api.system_from_spec(examples.get(name[5:]))
+            return name, env, s.poincare_build_info.strip()
         elif name.startswith("lyap_"):
             s = api.system_from_spec(examples.get(name[5:]))
             return name, env, s.lyapunov_build_info.strip()
