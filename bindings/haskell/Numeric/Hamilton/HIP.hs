@@ -50,6 +50,11 @@ module Numeric.Hamilton.HIP
   , lyapunovStepsBatch
   , SectionHits(..)
   , poincareStepsBatch
+  , Gate(..)
+  , Exits(..)
+  , exitAlive
+  , exitNonfinite
+  , exitStepsBatch
   , evolveHamEnsemble
     -- * ensembles resident in HBM, several GPUs from one process
   , DeviceEnsemble
@@ -218,6 +223,9 @@ foreign import ccall safe "hamk_lyapunov_steps"
 foreign import ccall safe "hamk_poincare_steps"
   c_poincare_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32 -> Double -> Double -> Int32 -> Int32
                    -> Ptr Double -> Ptr Double -> Ptr Double -> Ptr Int32 -> Int64 -> Ptr Int32 -> Int32 -> IO CInt
+foreign import ccall safe "hamk_exit_steps"
+  c_exit_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Ptr Gate -> Int32 -> Ptr Int32 -> Ptr Double
+               -> Ptr Double -> Ptr Double -> Int64 -> Ptr Int32 -> Int32 -> IO CInt
 foreign import ccall safe "hamk_checkpoint_write"
   c_ck_write :: CString -> Int32 -> Int64 -> Ptr Double -> Ptr Double -> Int32 -> Int64 -> Word64 -> Double -> IO CInt
 foreign import ccall safe "hamk_checkpoint_info"
@@ -566,6 +574,51 @@ poincareStepsBatch dt k coord level period direction start step0 (HipSystem h) e
       "poincareSteps"
   hits <- SectionHits rows <$> VS.unsafeFreeze hq <*> VS.unsafeFreeze hp <*> VS.unsafeFreeze ht <*> VS.unsafeFreeze hn
   pure (e', hits)
+
+-- | One gate of 'exitStepsBatch': component @gateCoord@ of @[q; p]@ must stay in @[gateLo, gateHi]@; a bound may be infinite.
+--   @struct hamk_gate { int32 coord, reserved; double lo, hi; }@ (24 bytes).
+data Gate = Gate { gateCoord :: !Int32, gateLo :: !Double, gateHi :: !Double }
+
+instance Storable Gate where
+  sizeOf _ = 24
+  alignment _ = 8
+  peek p = Gate <$> peekByteOff p 0 <*> peekByteOff p 8 <*> peekByteOff p 16
+  poke p (Gate c lo hi) = pokeByteOff p 0 c >> pokeByteOff p 4 (0 :: Int32) >> pokeByteOff p 8 lo >> pokeByteOff p 16 hi
+
+-- | @HAMK_EXIT_ALIVE@ / @HAMK_EXIT_NONFINITE@ of include/hamk.h.
+exitAlive, exitNonfinite :: Int32
+exitAlive = -1
+exitNonfinite = -2
+
+-- | What 'exitStepsBatch' keeps per trajectory: the code ('exitAlive' still running, @2 g + side@ stopped by gate @g@ through its
+--   lower / upper bound, 'exitNonfinite'), the exit time in units of @dt@ and the state at the exit (@[n][B]@ each).
+data Exits = Exits
+  { exitCode :: !(VS.Vector Int32)
+  , exitTimes :: !(VS.Vector Double)
+  , exitPositions :: !(VS.Vector Double)
+  , exitMomenta :: !(VS.Vector Double)
+  }
+
+-- | First-exit times fused with RK4 (no counterpart in the reference): up to @k@ RK4 steps of @dt@; a trajectory whose state has
+--   left one of the 1 to 4 gates stops, its exit located inside the step on RK4's cubic continuous extension, and a wavefront
+--   whose trajectories have all stopped ends its stepping.  A stopped trajectory's state is the end of its exit step.  @Nothing@
+--   starts a new run; @Just exits@ with @step0@ = the steps taken so far continues one bit for bit.  One trajectory per lane:
+--   @n <= 16@.
+exitStepsBatch :: forall m n. KnownNat n => Double -> Int -> [Gate] -> Maybe Exits -> Int64 -> HipSystem m n -> Ensemble n
+               -> IO (Ensemble n, Exits)
+exitStepsBatch dt k gates start step0 (HipSystem h) e = withForeignPtr h $ \s -> do
+  let nb = ensSize e
+      nq = VS.length (ensPositions e)
+      begin f z = maybe (pure z) (pure . f) start
+  xc <- VS.thaw =<< begin exitCode (VS.replicate nb exitAlive)
+  xt <- VS.thaw =<< begin exitTimes (VS.replicate nb 0)
+  xq <- VS.thaw =<< begin exitPositions (VS.replicate nq 0)
+  xp <- VS.thaw =<< begin exitMomenta (VS.replicate nq 0)
+  e' <- withArrayLen gates $ \ng pg -> VSM.unsafeWith xc $ \pc -> VSM.unsafeWith xt $ \pt -> VSM.unsafeWith xq $ \pxq -> VSM.unsafeWith xp $ \pxp ->
+    inPlace e (\b pq pp -> c_exit_steps s b pq pp dt (fromIntegral k) pg (fromIntegral ng) pc pt pxq pxp step0 nullPtr memHost)
+      "exitSteps"
+  exits <- Exits <$> VS.unsafeFreeze xc <*> VS.unsafeFreeze xt <*> VS.unsafeFreeze xq <*> VS.unsafeFreeze xp
+  pure (e', exits)
 
 -- | 'evolveHam' (Hamilton.hs:433-462) for every member: one ensemble per requested time,
 --   element 0 being the initial ensemble.

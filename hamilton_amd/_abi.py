@@ -69,6 +69,11 @@ class HamkOptions(ctypes.Structure):
 
 
 # name -> (restype, argtypes); mirrors include/hamk.h declaration by declaration
+class hamk_gate(ctypes.Structure):
+    """include/hamk.h hamk_gate: one gate of hamk_exit_steps."""
+    _fields_ = [("coord", ctypes.c_int32), ("reserved", ctypes.c_int32), ("lo", ctypes.c_double), ("hi", ctypes.c_double)]
+
+
 SIGNATURES = {
     "hamk_system_create": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(HamkOp), _i32, ctypes.POINTER(ctypes.c_int32),
@@ -107,6 +112,9 @@ SIGNATURES = {
     "hamk_poincare_steps": (ctypes.c_int, [_h, _i64, _dp, _dp, _f64, _i32, _i32, _f64, _f64, _i32, _i32, _dp, _dp, _dp, _ip, _i64, _ip, _i32]),
     "hamk_poincare_source": (ctypes.c_char_p, [_h]),
     "hamk_poincare_build_info": (ctypes.c_char_p, [_h]),
+    "hamk_exit_steps": (ctypes.c_int, [_h, _i64, _dp, _dp, _f64, _i32, ctypes.c_void_p, _i32, _ip, _dp, _dp, _dp, _i64, _ip, _i32]),
+    "hamk_exit_source": (ctypes.c_char_p, [_h]),
+    "hamk_exit_build_info": (ctypes.c_char_p, [_h]),
     "hamk_system_set_gsl_api": (ctypes.c_int, [_h, _i32]),
     "hamk_system_get_gsl_api": (_i32, [_h]),
     "hamk_system_code_object": (_i64, [_h, _i32, ctypes.c_void_p, _i64]),

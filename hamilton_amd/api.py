@@ -241,7 +241,7 @@ class System:
         text = fn(self._h)
         if text is None:
             msg = _abi.lib().hamk_last_error().decode("utf-8", "replace")
-            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper", "the Poincare-section stepper")) or "unsupported" in msg
+            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper", "the Poincare-section stepper", "the exit-time stepper")) or "unsupported" in msg
             raise HamkError(_abi.HAMK_ERR_UNSUPPORTED if unsupported else _abi.HAMK_ERR_COMPILE, msg)
         return text.decode()
 
@@ -274,6 +274,16 @@ class System:
     def poincare_build_info(self) -> str:
         """One `build_info`-format line for hamk_psec_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
         return self._symplectic_text(_abi.lib().hamk_poincare_build_info)
+
+    @property
+    def exit_source(self) -> str:
+        """Source of the exit-time stepper's companion module (hamk_exit_source; builds it if needed, needs no GPU)."""
+        return self._symplectic_text(_abi.lib().hamk_exit_source)
+
+    @property
+    def exit_build_info(self) -> str:
+        """One `build_info`-format line for hamk_exit_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
+        return self._symplectic_text(_abi.lib().hamk_exit_build_info)
 
     def kernel_bytes(self, kernel: str) -> int:
         return int(_abi.lib().hamk_system_kernel_bytes(self._h, kernel.encode()))
@@ -710,6 +720,82 @@ def poincareSteps(dt: float, nsteps: int, s: System, ph: Phase, coord: int, leve
     s._after(st, qa.single, "poincareSteps")
     drop = (lambda x: x[..., 0]) if qa.single else (lambda x: x)
     return Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Hits(drop(hq), drop(hp), drop(ht), drop(hn))
+
+
+class Exits:
+    """What exitSteps keeps per trajectory: `code` [B] (int32: -1 still running, 2 g + side stopped by gate g through its lower /
+    upper bound, -2 stopped because the state stopped being finite), `t` [B] (the exit time in units of dt: steps taken + the
+    fraction of the exit step) and `q`, `p` [n, B] (the state at the exit).  Entries of running trajectories hold what they held at
+    entry (zero for a new run).  For one trajectory the B axis is dropped."""
+
+    def __init__(self, code, t, q, p):
+        self.code = code
+        self.t = t
+        self.q = q
+        self.p = p
+
+    def __repr__(self):
+        return f"Exits {{code = {self.code!r}, t = {self.t!r}}}"
+
+
+def _gate_array(gates):
+    """[(coord, lo, hi), ...] -> a ctypes array of hamk_gate (host memory, as the ABI wants it)."""
+    gates = list(gates)
+    arr = (_abi.hamk_gate * max(1, len(gates)))()
+    for g, (coord, lo, hi) in enumerate(gates):
+        arr[g].coord, arr[g].reserved, arr[g].lo, arr[g].hi = int(coord), 0, float(lo), float(hi)
+    return arr, len(gates)
+
+
+def exitSteps(dt: float, nsteps: int, s: System, ph: Phase, gates, exits: Optional[Exits] = None, step0: int = 0, inplace: bool = False):
+    """First-exit times fused with RK4 (hamk_exit_steps; no reference counterpart): up to `nsteps` RK4 steps of `dt`; after every
+    step a trajectory whose state has left a gate stops -- `gates`: 1 to 4 tuples (coord, lo, hi), component `coord` of [q; p]
+    (coord < n: positions, else momenta) must stay in [lo, hi], either bound may be infinite -- and a wavefront whose trajectories
+    have all stopped ends its stepping.  Returns (Phase, Exits): a stopped trajectory's state is the END of its exit step,
+    Exits.q / .p the state at the exit, located inside the step on RK4's cubic continuous extension.  exits=None: a new run (every
+    code -1); passing the returned Exits back with step0 = the steps taken so far continues the run bit for bit.  inplace=True
+    advances the given arrays (state, and the Exits where given) without copying.  One trajectory per lane: n <= 16."""
+    qa, pa = _pair(ph.positions, "positions", ph.momenta, "momenta", s.n)
+    if inplace:
+        _in_place(qa, ph.positions, "positions"); _in_place(pa, ph.momenta, "momenta")
+    q, p = (qa.a, pa.a) if inplace else (qa.clone(), pa.clone())
+    if exits is None:
+        code, te = qa.like(None, "i4", zero=True), qa.like(None, zero=True)
+        code -= 1
+        eq, ep = qa.like(s.n, zero=True), qa.like(s.n, zero=True)
+    else:
+        bufs = []
+        for a, shape, name, f8 in ((exits.code, (qa.B,), "exits.code", False), (exits.t, (qa.B,), "exits.t", True),
+                                   (exits.q, (s.n, qa.B), "exits.q", True), (exits.p, (s.n, qa.B), "exits.p", True)):
+            if _is_torch(a) != qa.device or (qa.device and a.device != qa.a.device):
+                raise ValueError(f"{name} must live in the memory of the state")
+            if not qa.device:
+                a = np.asarray(a)
+            want = torch.float64 if (f8 and qa.device) else torch.int32 if qa.device else np.float64 if f8 else np.int32
+            if a.dtype != want or int(np.prod(a.shape)) != int(np.prod(shape)):
+                raise ValueError(f"{name}: expected {'float64' if f8 else 'int32'} of shape {shape}")
+            b = a.reshape(shape)
+            if qa.device:
+                b = b.contiguous()
+                same = b.data_ptr() == a.data_ptr()
+                b = b if inplace else b.clone()
+            else:
+                b = np.ascontiguousarray(b)
+                same = b.ctypes.data == a.ctypes.data
+                b = b if inplace else b.copy()
+            if inplace and not same:
+                raise ValueError(f"inplace=True needs {name} contiguous")
+            bufs.append(b)
+        code, te, eq, ep = bufs
+    garr, ngates = _gate_array(gates)
+    # zeroed: with nothing to do (nsteps = 0, an empty ensemble) the call returns HAMK_OK without writing status
+    st = qa.like(None, "i4", zero=True)
+    with s._on(qa):
+        _abi.check(_abi.lib().hamk_exit_steps(s._h, qa.B, _ptr(q), _ptr(p), float(dt), int(nsteps), ctypes.addressof(garr), ngates, _ptr(code), _ptr(te),
+                                              _ptr(eq), _ptr(ep), int(step0), _ptr(st), qa.mem))
+    s._after(st, qa.single, "exitSteps")
+    drop = (lambda x: x[..., 0]) if qa.single else (lambda x: x)
+    return Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Exits(drop(code), drop(te), drop(eq), drop(ep))
 
 
 # ---------------------------------------------------------------------------------------

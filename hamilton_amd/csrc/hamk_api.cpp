@@ -708,7 +708,7 @@ int hamk_rk4_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, i
 }
 
 // ---- the lane variant's companion modules: symplectic stepping (hamk_symp.hpp), Lyapunov stepping (hamk_lyap.hpp), ------
-// ---- Poincare sections (hamk_psec.hpp)
+// ---- Poincare sections (hamk_psec.hpp), first-exit times (hamk_exit.hpp)
 // The lane variant of a handle that can run a companion's stepper, that companion module built: n <= 16 and no other mapping
 // stated.  AUTO never leaves the lane mapping here, whatever B is (its small-ensemble rule for 11 <= n <= 16 was measured on RK4).
 static int companion_variant(hamk_system* s, CompanionKind kind, Variant** out) {
@@ -747,6 +747,8 @@ const char* hamk_lyapunov_source(hamk_system* s) { return companion_text(s, COMP
 const char* hamk_lyapunov_build_info(hamk_system* s) { return companion_text(s, COMPANION_LYAP, true); }
 const char* hamk_poincare_source(hamk_system* s) { return companion_text(s, COMPANION_PSEC, false); }
 const char* hamk_poincare_build_info(hamk_system* s) { return companion_text(s, COMPANION_PSEC, true); }
+const char* hamk_exit_source(hamk_system* s) { return companion_text(s, COMPANION_EXIT, false); }
+const char* hamk_exit_build_info(hamk_system* s) { return companion_text(s, COMPANION_EXIT, true); }
 
 int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t order,
                           int32_t iters, double* residual, int32_t* status, int32_t mem) {
@@ -834,6 +836,53 @@ int hamk_poincare_steps(hamk_system* s, int64_t B, double* q, double* p, double 
   TRY(st.inout(nhit, (size_t)B, &c.nhit));
   TRY(st.out(status, (size_t)B, &dst));
   TRY(launch_psec(s, B, xq, xp, c, dst));
+  return st.finish();
+}
+
+int hamk_exit_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, const hamk_gate* gates, int32_t ngates,
+                    int32_t* code, double* texit, double* qexit, double* pexit, int64_t step0, int32_t* status, int32_t mem) {
+  TRY(check_call(s, B, mem));
+  if (!q || !p || !gates || !code || !texit) return fail(HAMK_ERR_INVALID, "null q / p / gates / code / texit");
+  if ((qexit == nullptr) != (pexit == nullptr)) return fail(HAMK_ERR_INVALID, "qexit and pexit: both null or both given");
+  if (nsteps < 0) return fail(HAMK_ERR_INVALID, "negative nsteps");
+  if (ngates < 1 || ngates > HAMK_EXIT_MAX_GATES) return fail(HAMK_ERR_INVALID, "ngates must be 1 .. " + std::to_string(HAMK_EXIT_MAX_GATES));
+  const int64_t n = s->base.n;
+  ExitCall c{dt, nsteps, {}, nullptr, nullptr, nullptr, nullptr, step0};
+  std::memset(&c.gates, 0, sizeof c.gates);
+  for (int g = 0; g < HAMK_EXIT_MAX_GATES; ++g) {              // the rows beyond ngates: a gate that never fires
+    const bool given = g < ngates;
+    if (given) {
+      const std::string which = "gate " + std::to_string(g) + ": ";
+      if (gates[g].coord < 0 || gates[g].coord >= 2 * n)
+        return fail(HAMK_ERR_INVALID, which + "coord must be 0 .. 2n - 1 (q[coord], or p[coord - n]); this system has n = " + std::to_string(n));
+      if (std::isnan(gates[g].lo) || std::isnan(gates[g].hi)) return fail(HAMK_ERR_INVALID, which + "a bound is NaN (lo / hi may be infinite)");
+      if (!(gates[g].lo < gates[g].hi)) return fail(HAMK_ERR_INVALID, which + "lo must be below hi");
+    }
+    c.gates.coord[g] = given ? gates[g].coord : 0;
+    c.gates.lo[g] = given ? gates[g].lo : -HUGE_VAL;
+    c.gates.hi[g] = given ? gates[g].hi : HUGE_VAL;
+  }
+  c.gates.ngates = ngates;
+  if (!std::isfinite(dt)) return fail(HAMK_ERR_INVALID, "dt is not finite");
+  if (step0 < 0) return fail(HAMK_ERR_INVALID, "negative step0");
+  if (step0 > (INT64_C(1) << 52)) return fail(HAMK_ERR_INVALID, "step0 exceeds 2^52: step0 + step index would not be exact as a double");
+  Variant* v = nullptr;
+  TRY(companion_variant(s, COMPANION_EXIT, &v));
+  if (B == 0 || nsteps == 0) return HAMK_OK;
+  TRY(companion_load(s, v, COMPANION_EXIT));
+  Stager st(s, mem);
+  const size_t cnt = (size_t)n * B;
+  double *xq, *xp; int32_t* dst;
+  TRY(st.inout(q, cnt, &xq));
+  TRY(st.inout(p, cnt, &xp));
+  TRY(st.inout(code, (size_t)B, &c.code));                     // inout: a stopped lane's memory is never written and must survive the staging
+  TRY(st.inout(texit, (size_t)B, &c.texit));
+  if (qexit) {
+    TRY(st.inout(qexit, cnt, &c.qexit));
+    TRY(st.inout(pexit, cnt, &c.pexit));
+  }
+  TRY(st.out(status, (size_t)B, &dst));
+  TRY(launch_exit(s, B, xq, xp, c, dst));
   return st.finish();
 }
 

@@ -46,6 +46,9 @@ static const char kLyapHeader[] =
 static const char kPsecHeader[] =
 #include "hamk_psec_src.inc"
     ;
+static const char kExitHeader[] =
+#include "hamk_exit_src.inc"
+    ;
 
 // What distinguishes the companion modules of the lane variant (hamk_host.h CompanionKind): the header that defines the one
 // kernel, the macro that instantiates it, and what a refusal calls it.
@@ -62,6 +65,7 @@ const CompanionDesc kCompanions[COMPANION__COUNT] = {
     {"hamk_symp.hpp", kSympHeader, sizeof kSympHeader, "HAMK_INSTANTIATE_SYMP", "hamk_symp_steps_k", "the symplectic stepper"},
     {"hamk_lyap.hpp", kLyapHeader, sizeof kLyapHeader, "HAMK_INSTANTIATE_LYAP", "hamk_lyap_steps_k", "the Lyapunov stepper"},
     {"hamk_psec.hpp", kPsecHeader, sizeof kPsecHeader, "HAMK_INSTANTIATE_PSEC", "hamk_psec_steps_k", "the Poincare-section stepper"},
+    {"hamk_exit.hpp", kExitHeader, sizeof kExitHeader, "HAMK_INSTANTIATE_EXIT", "hamk_exit_steps_k", "the exit-time stepper"},
 };
 }  // namespace
 const char* companion_kernel_name(CompanionKind kind) { return kCompanions[kind].kernel; }
@@ -372,14 +376,14 @@ size_t chosen_kernel_bytes(const Variant* s, int k) {
   return kernel_code_bytes(s->use2[k] ? s->code2 : s->code, kKernelNames[k]);
 }
 
-// ---- the lane variant's companion modules (hamk_symp.hpp, hamk_lyap.hpp, hamk_psec.hpp) -------------------------------
+// ---- the lane variant's companion modules (hamk_symp.hpp, hamk_lyap.hpp, hamk_psec.hpp, hamk_exit.hpp) ---------------------------
 // A per-system module holds exactly the nine kernels of HAMK_INSTANTIATE (tests/test_abi.py counts its function symbols and
 // the rows of build_info), and its cache key covers the whole text of hamk_device.hpp: a tenth kernel there would move every
-// existing module.  So hamk_symp_steps_k, hamk_lyap_steps_k and hamk_psec_steps_k each live in a module of their own: the lane variant's generated
+// existing module.  So hamk_symp_steps_k, hamk_lyap_steps_k, hamk_psec_steps_k and hamk_exit_steps_k each live in a module of their own: the lane variant's generated
 // source -- the system's struct and #defines as they are, generate_source is not called again -- with its final
 // HAMK_INSTANTIATE(HamkSys) replaced by the include of the kind's header and its HAMK_INSTANTIATE_*(HamkSys).  One build with the
 // lane module's option list, through the same on-disk cache; the per-kernel choice between two builds (build_code) is not made
-// here -- DESIGN.md sections 11 to 13 list what the kernels spill.
+// here -- DESIGN.md sections 11 to 14 list what the kernels spill.
 int build_companion(Variant* v, CompanionKind kind, bool cache_on) {
   Variant::Companion& c = v->companion[kind];
   if (!c.code.empty()) return HAMK_OK;

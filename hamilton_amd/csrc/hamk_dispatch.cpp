@@ -359,6 +359,10 @@ int launch_psec(hamk_system* s, int64_t B, double* q, double* p, const PsecCall&
   return launch_kernel<sig_psec::hamk_psec_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].companion_fn[COMPANION_PSEC], s->cur->stream, B, 256, q, p, B, c.dt, c.nsteps, c.coord,
                                                         c.level, c.period, c.direction, c.max_hits, c.qhit, c.phit, c.thit, c.nhit, c.step0, status);
 }
+int launch_exit(hamk_system* s, int64_t B, double* q, double* p, const ExitCall& c, int* status) {
+  return launch_kernel<sig_exit::hamk_exit_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].companion_fn[COMPANION_EXIT], s->cur->stream, B, 256, q, p, B, c.dt, c.nsteps, c.gates,
+                                                        c.code, c.texit, c.qexit, c.pexit, c.step0, status);
+}
 int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx) {
   return launch_kernel<sig::hamk_sample_k>::on(d->sample_fn, d->stream, B, 256, q, qd, B, first_index, seed, n, bx);
 }

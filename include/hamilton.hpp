@@ -502,6 +502,32 @@ inline Phase poincareSteps(double dt, int nsteps, System& s, const Phase& ph, in
                             hits.positions.data(), hits.momenta.data(), hits.times.data(), hits.count.data(), step0, s.last_status.data(), HAMK_MEM_HOST));
   return out;
 }
+// First-exit times fused with RK4 (hamk_exit_steps; no reference counterpart): up to `nsteps` RK4 steps of dt; a trajectory whose
+// state has left a gate -- component `coord` of [q; p] outside [lo, hi], 1 to HAMK_EXIT_MAX_GATES gates -- stops; n <= 16.
+// code: [B], HAMK_EXIT_ALIVE running, 2 g + side stopped by gate g through its lower / upper bound, HAMK_EXIT_NONFINITE; t: [B], in
+// units of dt; positions / momenta: [n][B], the state at the exit.  An EMPTY Exits starts a new run (every code HAMK_EXIT_ALIVE);
+// feeding the same Exits to the next call with step0 = the steps taken so far continues the run bit for bit.  A stopped
+// trajectory's state in the returned Phase is the END of its exit step.
+struct Exits {
+  std::vector<int32_t> code;
+  std::vector<double> t, positions, momenta;
+};
+inline Phase exitSteps(double dt, int nsteps, System& s, const Phase& ph, const std::vector<hamk_gate>& gates, Exits& exits, int64_t step0 = 0) {
+  Phase out = ph;
+  const size_t nb = (size_t)ph.B;
+  if (exits.code.empty() && exits.t.empty() && exits.positions.empty() && exits.momenta.empty()) {
+    exits.code.assign(nb, HAMK_EXIT_ALIVE);
+    exits.t.assign(nb, 0.0);
+    exits.positions.assign(ph.positions.size(), 0.0);
+    exits.momenta.assign(ph.momenta.size(), 0.0);
+  }
+  if (exits.code.size() != nb || exits.t.size() != nb || exits.positions.size() != ph.positions.size() || exits.momenta.size() != ph.momenta.size())
+    throw std::invalid_argument("exitSteps: exits must describe the ensemble of the state");
+  s.last_status.assign(nb, 0);
+  check(hamk_exit_steps(s.handle(), ph.B, out.positions.data(), out.momenta.data(), dt, nsteps, gates.data(), (int32_t)gates.size(), exits.code.data(),
+                        exits.t.data(), exits.positions.data(), exits.momenta.data(), step0, s.last_status.data(), HAMK_MEM_HOST));
+  return out;
+}
 
 // ---------------------------------------------------------------------------------------
 // Ensembles resident in HBM (no reference counterpart: the reference holds one trajectory on the
@@ -589,6 +615,13 @@ inline void poincareSteps(double dt, int nsteps, System& s, DevicePhase& d, int 
                           DeviceArray& qhit, DeviceArray& phit, DeviceArray& thit, DeviceArray& nhit, int64_t step0 = 0) {      // in place, asynchronous
   check(hamk_poincare_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, coord, level, period, direction, max_hits,
                             qhit.as<double>(), phit.as<double>(), thit.as<double>(), nhit.as<int32_t>(), step0, d.status.as<int32_t>(), HAMK_MEM_DEVICE));
+}
+// code: B int32, texit: B doubles, qexit, pexit: n B doubles (both may be an empty DeviceArray's null) -- all on the device, the
+// caller's, initialised by the caller (code = HAMK_EXIT_ALIVE for a new run); the gates are host memory
+inline void exitSteps(double dt, int nsteps, System& s, DevicePhase& d, const std::vector<hamk_gate>& gates, DeviceArray& code, DeviceArray& texit,
+                      DeviceArray& qexit, DeviceArray& pexit, int64_t step0 = 0) {      // in place, asynchronous
+  check(hamk_exit_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, gates.data(), (int32_t)gates.size(),
+                        code.as<int32_t>(), texit.as<double>(), qexit.as<double>(), pexit.as<double>(), step0, d.status.as<int32_t>(), HAMK_MEM_DEVICE));
 }
 inline void stepHam(double r, System& s, DevicePhase& d) {                     // :390-402, in place, asynchronous
   check(hamk_step_ham_batch(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), r, d.status.as<int32_t>(), nullptr, HAMK_MEM_DEVICE));

@@ -25,6 +25,7 @@
  *   (no counterpart; a structure-preserving fixed step) hamk_symplectic_steps (implicit midpoint, order 2 / 4)
  *   (no counterpart; which trajectories are chaotic)    hamk_lyapunov_steps   (largest Lyapunov exponent, fused with RK4)
  *   (no counterpart; the surface of section)            hamk_poincare_steps   (crossings recorded inside a fused RK4 launch)
+ *   (no counterpart; first-exit times)                  hamk_exit_steps       (when and where a trajectory leaves a box; it then stops)
  *
  * The reference evaluates ONE trajectory per call on the CPU through `ad`
  * (AD), hmatrix (LAPACK/BLAS) and hmatrix-gsl (GSL odeiv).  This library
@@ -427,6 +428,55 @@ int hamk_poincare_steps(hamk_system* s, int64_t B, double* q, double* p, double 
  * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
 const char* hamk_poincare_source(hamk_system* s);
 const char* hamk_poincare_build_info(hamk_system* s);
+
+/* First-exit times fused with classic RK4: up to `nsteps` RK4 steps of dt IN PLACE on q, p (the right-hand side and the step of
+ * the Poincare-section stepper, one trajectory per lane), and after every step the test whether the trajectory has left a region; a trajectory
+ * that has left STOPS, and a wavefront whose trajectories have all stopped ends its stepping: finished work is dropped.
+ *   The region.  1 .. HAMK_EXIT_MAX_GATES gates in HOST memory (whatever mem says), each a component of y = [q; p] -- coord in
+ *   [0, 2n): q[coord] for coord < n, p[coord - n] otherwise -- and a closed interval [lo, hi], lo < hi, either bound may be
+ *   infinite; `reserved` is ignored.
+ *   Per-trajectory state, READ, UPDATED AND WRITTEN BACK.  code[B]: HAMK_EXIT_ALIVE (-1) still running; 2 g + side >= 0 stopped by
+ *   gate g through its lower (side 0) or upper (side 1) bound; HAMK_EXIT_NONFINITE (-2) stopped because the state stopped being
+ *   finite.  texit[B], in units of dt.  qexit, pexit [n][B]: the state at the exit; both NULL or both given.  A trajectory is
+ *   alive iff its code at entry is exactly -1 (a new run: every code -1); any other value counts as stopped, and of a trajectory
+ *   stopped at entry nothing is read but its code and nothing is written but status (0): q, p, code, texit, qexit, pexit keep
+ *   their bits.
+ *   A step of an alive trajectory from y0 to y1.  Any component of y1 not finite: code -2, texit = step0 + step index + 1,
+ *   HAMK_ST_NONFINITE, qexit / pexit untouched.  Otherwise gate g FIRES where its component at y1 lies outside [lo, hi]; the target
+ *   is the violated bound, and theta in [0, 1] with Yc(theta) = target is located on RK4's third-order continuous extension from the
+ *   secant value by FOUR Newton iterations, theta clamped to [0, 1] after each, a non-finite update leaving theta as it was (see
+ *   the Poincare-section stepper above).  A component already outside at y0 -- an alive trajectory's first step only -- has theta = 0.  The firing
+ *   gate with the smallest theta wins, on a tie the lowest index: code = 2 g + side, texit = (double)(step0 + step index) + theta,
+ *   step0 being the caller's count of steps already taken; qexit, pexit receive Y(theta) in all 2n components, the gate component
+ *   as computed, not snapped to the bound.  Either way q, p become y1, the END of the exit step, and are not advanced again.
+ *   So: N steps in one call equal N1 + N2 in two calls with step0 = N1 and the arrays carried over, bit for bit on every output;
+ *   a stopped trajectory's q, p are those of a call with nsteps = floor(texit) - step0 + 1 (floor(texit) - step0 for code -2);
+ *   while a trajectory is alive its q, p do not depend on the gates, nor on any other trajectory.
+ *   q, p, gates, code, texit are required; status may be NULL.  status: HAMK_ST_SINGULAR from any right-hand side of a step the
+ *   trajectory was alive in, HAMK_ST_NONFINITE with code -2.
+ *   HAMK_ERR_INVALID: a null handle or required array, exactly one of qexit / pexit, B < 0, nsteps < 0, ngates outside
+ *   1 .. HAMK_EXIT_MAX_GATES, a coord outside [0, 2n), a NaN bound or lo >= hi, dt not finite, step0 < 0 or beyond 2^52, an unknown
+ *   mem.  One trajectory per lane: n <= 16; HAMK_ERR_UNSUPPORTED for n > 16 or a handle whose options state HAMK_MAP_QUAD /
+ *   HAMK_MAP_WAVE; mapping = HAMK_AUTO ALWAYS runs on the one-trajectory-per-lane module, whatever B is.
+ *   HAMK_MEM_DEVICE: asynchronous on the handle's stream; HAMK_MEM_HOST: staged (code, texit, qexit, pexit both ways), returns with
+ *   the results in place.  B == 0 or nsteps == 0: HAMK_OK, nothing launched and nothing written.  The kernel (hamk_exit.hpp) lives
+ *   in a companion module of the lane module, built the first time one of these three entry points asks for it; the first-use
+ *   self-check does not cover it.  No reference counterpart.                                                              */
+#define HAMK_EXIT_MAX_GATES 4
+#define HAMK_EXIT_ALIVE     -1
+#define HAMK_EXIT_NONFINITE -2
+typedef struct hamk_gate {
+  int32_t coord;
+  int32_t reserved;
+  double lo, hi;
+} hamk_gate;
+int hamk_exit_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, const hamk_gate* gates,
+                    int32_t ngates, int32_t* code, double* texit, double* qexit, double* pexit, int64_t step0, int32_t* status,
+                    int32_t mem);
+/* Source / one build_info-format line (kernel, bytes, spilled SGPRs and VGPRs, allocated VGPRs, function symbols) of that
+ * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
+const char* hamk_exit_source(hamk_system* s);
+const char* hamk_exit_build_info(hamk_system* s);
 
 /* stepHam dt: adaptive RKF45 with GSL's standard controller from 0 to dt,
  * h0 = dt/100, eps_abs = eps_rel = 1.49012e-08, IN PLACE.  Hamilton.hs:390-402,

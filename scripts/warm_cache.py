@@ -97,6 +97,9 @@ def jobs():
     # the Poincare-section stepper's companion module (hamk_psec.hpp) of the systems tests/test_gpu_poincare.py steps, its two anchors included
     for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "anchor_rotor", "anchor_oscillator"):
         out.append((f"psec_{n}", {}, False))
+    # the exit-time stepper's companion module (hamk_exit.hpp) of the systems tests/test_gpu_exit.py steps, its three anchors included
+    for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "anchor_rotor", "anchor_oscillator", "anchor_free"):
+        out.append((f"exit_{n}", {}, False))
     return rect + out
 
 
@@ -140,6 +143,12 @@ def build(job):
         elif name.startswith("psec_anchor_"):
             import test_poincare
             return name, env, test_poincare.anchor_system(name[12:]).poincare_build_info.strip()
+        elif name.startswith("exit_anchor_"):
+            import test_exit
+            return name, env, test_exit.anchor_system(name[12:]).exit_build_info.strip()
+        elif name.startswith("exit_"):
+            s = api.system_from_spec(examples.get(name[5:]))
+            return name, env, s.exit_build_info.strip()
         elif name.startswith("psec_"):
             s = api.system_from_spec(examples.get(name[5:]))
             return name, env, s.poincare_build_info.strip()
