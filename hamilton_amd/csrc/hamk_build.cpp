@@ -49,23 +49,27 @@ static const char kPsecHeader[] =
 static const char kExitHeader[] =
 #include "hamk_exit_src.inc"
     ;
+static const char kFusedRk4Header[] =
+#include "hamk_fused_rk4_src.inc"
+    ;
 
 // What distinguishes the companion modules of the lane variant (hamk_host.h CompanionKind): the header that defines the one
-// kernel, the macro that instantiates it, and what a refusal calls it.
+// kernel, whether that header includes hamk_fused_rk4.hpp, the macro that instantiates it, and what a refusal calls it.
 namespace {
 struct CompanionDesc {
   const char* header_name;
   const char* header_src;
   size_t header_bytes;       // sizeof the embedded text (its terminating NUL included), as the cache key has always fed it
+  bool fused_rk4;            // the header includes hamk_fused_rk4.hpp: a further header of the program and of the cache key
   const char* instantiate;
   const char* kernel;
   const char* what;
 };
 const CompanionDesc kCompanions[COMPANION__COUNT] = {
-    {"hamk_symp.hpp", kSympHeader, sizeof kSympHeader, "HAMK_INSTANTIATE_SYMP", "hamk_symp_steps_k", "the symplectic stepper"},
-    {"hamk_lyap.hpp", kLyapHeader, sizeof kLyapHeader, "HAMK_INSTANTIATE_LYAP", "hamk_lyap_steps_k", "the Lyapunov stepper"},
-    {"hamk_psec.hpp", kPsecHeader, sizeof kPsecHeader, "HAMK_INSTANTIATE_PSEC", "hamk_psec_steps_k", "the Poincare-section stepper"},
-    {"hamk_exit.hpp", kExitHeader, sizeof kExitHeader, "HAMK_INSTANTIATE_EXIT", "hamk_exit_steps_k", "the exit-time stepper"},
+    {"hamk_symp.hpp", kSympHeader, sizeof kSympHeader, false, "HAMK_INSTANTIATE_SYMP", "hamk_symp_steps_k", "the symplectic stepper"},
+    {"hamk_lyap.hpp", kLyapHeader, sizeof kLyapHeader, true, "HAMK_INSTANTIATE_LYAP", "hamk_lyap_steps_k", "the Lyapunov stepper"},
+    {"hamk_psec.hpp", kPsecHeader, sizeof kPsecHeader, true, "HAMK_INSTANTIATE_PSEC", "hamk_psec_steps_k", "the Poincare-section stepper"},
+    {"hamk_exit.hpp", kExitHeader, sizeof kExitHeader, true, "HAMK_INSTANTIATE_EXIT", "hamk_exit_steps_k", "the exit-time stepper"},
 };
 }  // namespace
 const char* companion_kernel_name(CompanionKind kind) { return kCompanions[kind].kernel; }
@@ -140,6 +144,7 @@ static CacheKey cache_key(const Variant* s, const std::vector<const char*>& opts
   if (s->mapping == HAMK_MAP_WAVE) feed(kWaveHeader, sizeof kWaveHeader);
   if (s->mapping == HAMK_MAP_QUAD) feed(kQuadHeader, sizeof kQuadHeader);
   if (companion != COMPANION_NONE) feed(kCompanions[companion].header_src, kCompanions[companion].header_bytes);   // a companion module's source includes its header as well
+  if (companion != COMPANION_NONE && kCompanions[companion].fused_rk4) feed(kFusedRk4Header, sizeof kFusedRk4Header);   // ... and that header this one
   for (const char* o : opts) feed(o, std::strlen(o) + 1);
   feed(&major, sizeof major);
   feed(&minor, sizeof minor);
@@ -188,9 +193,10 @@ static void cache_store(const CacheKey& k, const std::vector<char>& code) {   //
 int compile_module(Variant* s, bool cache_on, bool no_machine_licm, std::vector<char>& code, CompanionKind companion) {
   hiprtcProgram prog = nullptr;
   const bool comp = companion != COMPANION_NONE;               // a companion's own header is the fourth of its program, nobody else's
-  const char* hdr_src[] = {kDeviceHeader, kWaveHeader, kQuadHeader, comp ? kCompanions[companion].header_src : nullptr};
-  const char* hdr_name[] = {"hamk_device.hpp", "hamk_wave.hpp", "hamk_quad.hpp", comp ? kCompanions[companion].header_name : nullptr};
-  hiprtcResult r = hiprtcCreateProgram(&prog, s->source.c_str(), "hamk_system.hip", comp ? 4 : 3, hdr_src, hdr_name);
+  const bool fused = comp && kCompanions[companion].fused_rk4;  // ... and the header the fused RK4 companions share the fifth of theirs
+  const char* hdr_src[] = {kDeviceHeader, kWaveHeader, kQuadHeader, comp ? kCompanions[companion].header_src : nullptr, kFusedRk4Header};
+  const char* hdr_name[] = {"hamk_device.hpp", "hamk_wave.hpp", "hamk_quad.hpp", comp ? kCompanions[companion].header_name : nullptr, "hamk_fused_rk4.hpp"};
+  hiprtcResult r = hiprtcCreateProgram(&prog, s->source.c_str(), "hamk_system.hip", fused ? 5 : (comp ? 4 : 3), hdr_src, hdr_name);
   if (r != HIPRTC_SUCCESS) return fail(HAMK_ERR_COMPILE, std::string("hiprtcCreateProgram: ") + hiprtcGetErrorString(r));
   std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast",
                                    "-fno-honor-nans", "-fno-signed-zeros"};

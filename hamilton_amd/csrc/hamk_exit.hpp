@@ -5,12 +5,11 @@
 // Per trajectory: the state y, a code (HAMK_EXIT_ALIVE = -1 running; 2 g + side >= 0 stopped by gate g through its lower (side 0) or
 // upper (side 1) bound; HAMK_EXIT_NONFINITE = -2 stopped because the state stopped being finite) and an exit time.  A lane is ALIVE
 // iff its code at entry is exactly -1.  One step of an alive lane:
-//     1.  y1 = RK4(y0, dt), keeping k1 and k2 + k3 beside the accumulator (k4 is what the last stage leaves in k), as hamk_psec.hpp
+//     1.  y1 = RK4(y0, dt), keeping k1 and k2 + k3 beside the accumulator (k4 is what the last stage leaves in k)
 //     2.  any component of y1 not finite: code = -2, texit = step0 + step index + 1, ST_NONFINITE, the exit state untouched
 //     3.  otherwise every gate g (a component c_g of y = [q; p] and a closed interval [lo_g, hi_g]) FIRES where y1[c_g] < lo_g or
 //         y1[c_g] > hi_g; its target is the violated bound.  theta_g in [0, 1] with Y_c(theta) = target on RK4's own third-order
-//         continuous extension (hamk_psec.hpp states it), from the secant value (target - y0c) / (y1c - y0c) by a FIXED number of
-//         Newton iterations (kExitNewton = 4), clamped to [0, 1] after each, a non-finite update leaving theta as it was; a component
+//         continuous extension, by hamk_fused_rk4.hpp's dense_root (that header states Y and the iteration); a component
 //         already outside [lo_g, hi_g] at y0 (an alive lane's first step only) has theta_g = 0.  The firing gate with the smallest
 //         theta wins, on a tie the lowest index: code = 2 g + side, texit = (double)(step0 + step index) + theta, in units of dt,
 //         and qexit, pexit receive Y(theta) in all 2n components -- the gate component as computed, not snapped to the bound
@@ -20,27 +19,25 @@
 // lanes only.  After every step `if (__ballot(alive) == 0) break;` -- a wave-uniform scalar branch -- drops the wavefront's remaining
 // steps; a wavefront with no alive lane at entry runs none.  Wavefronts of one block leave at different steps:
 //     NO BLOCK-WIDE BARRIER AND NO LDS MAY APPEAR INSIDE THE STEP LOOP (a barrier there would hang the block).
-// The right-hand side is ham_eqs<S, S::MODE_H> with its default TRIG_FULL, which needs neither.
+// What the loop calls in hamk_fused_rk4.hpp (the step, the component select, the root finder) needs neither.
 //
 // texit's two summands are the same whichever way a run is cut and code / texit / the exit state are read, updated and written
 // back: N steps in one call equal N1 + N2 in two calls with step0 = N1 and the arrays carried over, bit for bit.  While a lane is
 // alive its state's arithmetic does not involve the gates, nor any other lane.
 //
-// The step loop, the stage loop and the gate loop stay rolled: one copy of the right-hand side, one of Newton.  k1 and k2 + k3 are
-// kept by scalar selects on the wave-uniform stage index; a gate's bounds and component are picked by scalar selects on the
-// wave-uniform gate index and coord: no register array is indexed at run time.  The gates arrive BY VALUE (HamkGates, as HamkBoxes
-// does for hamk_sample_k).  Every store uses the lane's own index only, (i64)j * B + i.
+// The step loop and the gate loop stay rolled, as the stage loop does: one copy of the right-hand side, one of Newton.  A gate's
+// bounds and component are picked by scalar selects on the wave-uniform gate index: no register array is indexed at run time.  The
+// gates arrive BY VALUE (HamkGates, as HamkBoxes does for hamk_sample_k).  Every store uses the lane's own index only, (i64)j * B + i.
 //
 // This header rides beside hamk_device.hpp in a COMPANION module of the lane variant (hamk_build.cpp build_companion): the
 // variant's generated source with its HAMK_INSTANTIATE(HamkSys) replaced by HAMK_INSTANTIATE_EXIT(HamkSys).
 #pragma once
-#include "hamk_device.hpp"
+#include "hamk_fused_rk4.hpp"
 
 struct HamkGates { double lo[4], hi[4]; int coord[4]; int ngates; int reserved; };   // HAMK_EXIT_MAX_GATES = 4 (hamk.h); by value
 
 namespace hamk {
 
-constexpr int kExitNewton = 4;
 constexpr int kExitAlive = -1, kExitNonfinite = -2;
 
 template <class S>
@@ -67,25 +64,7 @@ HAMK_DEV void exit_body(double* __restrict__ q, double* __restrict__ p, i64 B, d
     if (__ballot(alive) == 0) break;                           // wave-uniform: nothing left to do in this wavefront
     double kq[N], kp[N], cq[N], cp[N], k1q[N], k1p[N], k23q[N], k23p[N];
     int sst = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) { kq[j] = 0.0; kp[j] = 0.0; cq[j] = aq[j]; cp[j] = ap[j]; k1q[j] = 0.0; k1p[j] = 0.0; k23q[j] = 0.0; k23p[j] = 0.0; }
-#pragma unroll 1
-    for (int sg = 0; sg < 4; ++sg) {
-      const double a = (sg == 0) ? 0.0 : ((sg == 3) ? dt : h2);   // wave-uniform: scalar selects
-      const double b = (sg == 0 || sg == 3) ? h6 : h3;
-      double yq[N], yp[N];
-#pragma unroll
-      for (int j = 0; j < N; ++j) { yq[j] = fma(a, kq[j], aq[j]); yp[j] = fma(a, kp[j], ap[j]); }
-      ham_eqs<S, S::MODE_H>(yq, yp, kq, kp, sst, tc);
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        cq[j] = fma(b, kq[j], cq[j]); cp[j] = fma(b, kp[j], cp[j]);
-        k1q[j] = (sg == 0) ? kq[j] : k1q[j]; k1p[j] = (sg == 0) ? kp[j] : k1p[j];                    // k1
-        const double sq = k23q[j] + kq[j], sp = k23p[j] + kp[j];
-        k23q[j] = (sg == 1) ? kq[j] : ((sg == 2) ? sq : k23q[j]);                                    // k2, then k2 + k3
-        k23p[j] = (sg == 1) ? kp[j] : ((sg == 2) ? sp : k23p[j]);
-      }
-    }
+    HAMK_RK4_STAGES(S, 1, aq, ap, dt, h2, h6, h3, kq, kp, cq, cp, k1q, k1p, k23q, k23p, sst, tc)
     bool stops = false;
     if (alive) {                                               // lane-divergent: arithmetic and stores only
       st |= sst;
@@ -106,30 +85,12 @@ HAMK_DEV void exit_body(double* __restrict__ q, double* __restrict__ p, i64 B, d
           const int coord = g == 0 ? gates.coord[0] : (g == 1 ? gates.coord[1] : (g == 2 ? gates.coord[2] : gates.coord[3]));
           const double lo = g == 0 ? gates.lo[0] : (g == 1 ? gates.lo[1] : (g == 2 ? gates.lo[2] : gates.lo[3]));
           const double hi = g == 0 ? gates.hi[0] : (g == 1 ? gates.hi[1] : (g == 2 ? gates.hi[2] : gates.hi[3]));
-          double y0c = 0.0, y1c = 0.0, k1c = 0.0, k23c = 0.0, k4c = 0.0;
-#pragma unroll
-          for (int j = 0; j < N; ++j) {
-            const bool isq = coord == j, isp = coord == j + N;
-            y0c = isq ? aq[j] : (isp ? ap[j] : y0c);
-            y1c = isq ? cq[j] : (isp ? cp[j] : y1c);
-            k1c = isq ? k1q[j] : (isp ? k1p[j] : k1c);
-            k23c = isq ? k23q[j] : (isp ? k23p[j] : k23c);
-            k4c = isq ? kq[j] : (isp ? kp[j] : k4c);
-          }
+          double y0c, y1c, k1c, k23c, k4c;
+          dense_component<N>(coord, aq, ap, cq, cp, k1q, k1p, k23q, k23p, kq, kp, y0c, y1c, k1c, k23c, k4c);
           const bool below = y1c < lo, above = y1c > hi;
           if (below || above) {
             const double target = below ? lo : hi;
-            double th = ::fmin(1.0, ::fmax(0.0, (target - y0c) / (y1c - y0c)));      // the secant value
-#pragma unroll
-            for (int it = 0; it < kExitNewton; ++it) {
-              const double t2 = th * th, t3 = t2 * th;
-              const double b1 = th - 1.5 * t2 + (2.0 / 3.0) * t3, b2 = t2 - (2.0 / 3.0) * t3, b4 = (2.0 / 3.0) * t3 - 0.5 * t2;
-              const double d1 = 1.0 - 3.0 * th + 2.0 * t2, d2 = 2.0 * th - 2.0 * t2, d4 = 2.0 * t2 - th;
-              const double gv = (y0c - target) + dt * (b1 * k1c + b2 * k23c + b4 * k4c);
-              const double dg = dt * (d1 * k1c + d2 * k23c + d4 * k4c);
-              const double tn = th - gv / dg;
-              th = is_nonfinite_bits(tn) ? th : ::fmin(1.0, ::fmax(0.0, tn));
-            }
+            double th = dense_root(y0c, y1c, k1c, k23c, k4c, target, dt);
             th = (y0c < lo || y0c > hi) ? 0.0 : th;            // outside already at y0: the step's start
             const bool wins = th < best;                       // strict: on a tie the lower index stays
             best = wins ? th : best;
@@ -141,7 +102,7 @@ HAMK_DEV void exit_body(double* __restrict__ q, double* __restrict__ p, i64 B, d
           code[i] = won;
           texit[i] = (double)(step0 + (i64)s) + best;
           if (qexit) {
-            const double t2 = best * best, t3 = t2 * best;
+            const double t2 = best * best, t3 = t2 * best;         // dense_weights(best), in place: hamk_fused_rk4.hpp says why
             const double b1 = best - 1.5 * t2 + (2.0 / 3.0) * t3, b2 = t2 - (2.0 / 3.0) * t3, b4 = (2.0 / 3.0) * t3 - 0.5 * t2;
 #pragma unroll
             for (int j = 0; j < N; ++j) {

@@ -14,10 +14,9 @@
 // carried over -- reproduce the one-call bits.
 //
 // The two trajectories go through ONE copy of the step: the inner loop advances `a` and then exchanges a and b, twice per step,
-// so the main trajectory's arithmetic is the shadow's instruction for instruction and depends on neither w nor d0.  The
-// right-hand side is ham_eqs<S, S::MODE_H> with its default TRIG_FULL, the instantiation of hamk_hameqs_k and hamk_symp_steps_k:
-// no LDS table.  The loops over intervals, steps, the two trajectories and the four stages all stay rolled: one copy of the
-// right-hand side, code size independent of the arguments.
+// so the main trajectory's arithmetic is the shadow's instruction for instruction and depends on neither w nor d0.  The step
+// is hamk_fused_rk4.hpp's HAMK_RK4_STAGES, which states the right-hand side and the rolled stage loop; the loops over intervals, steps
+// and the two trajectories stay rolled as well: one copy of the right-hand side, code size independent of the arguments.
 //
 // status: the OR of HAMK_ST_SINGULAR of every right-hand side (both trajectories), HAMK_ST_NONFINITE where the final state, w or
 // logsum is not finite (d = 0 gives log 0 = -inf and w = 0 / 0, flagged this way).
@@ -25,7 +24,7 @@
 // This header rides beside hamk_device.hpp in a COMPANION module of the lane variant (hamk_build.cpp build_companion): the
 // variant's generated source with its HAMK_INSTANTIATE(HamkSys) replaced by HAMK_INSTANTIATE_LYAP(HamkSys).
 #pragma once
-#include "hamk_device.hpp"
+#include "hamk_fused_rk4.hpp"
 
 namespace hamk {
 
@@ -54,19 +53,7 @@ HAMK_DEV void lyap_body(double* __restrict__ q, double* __restrict__ p, double* 
 #pragma unroll 1
       for (int t = 0; t < 2; ++t) {                           // t = 0: a is y, b is s; t = 1: the other way round
         double kq[N], kp[N], cq[N], cp[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) { kq[j] = 0.0; kp[j] = 0.0; cq[j] = aq[j]; cp[j] = ap[j]; }
-#pragma unroll 1
-        for (int sg = 0; sg < 4; ++sg) {
-          const double a = (sg == 0) ? 0.0 : ((sg == 3) ? dt : h2);   // wave-uniform: scalar selects
-          const double b = (sg == 0 || sg == 3) ? h6 : h3;
-          double yq[N], yp[N];
-#pragma unroll
-          for (int j = 0; j < N; ++j) { yq[j] = fma(a, kq[j], aq[j]); yp[j] = fma(a, kp[j], ap[j]); }
-          ham_eqs<S, S::MODE_H>(yq, yp, kq, kp, st, tc);
-#pragma unroll
-          for (int j = 0; j < N; ++j) { cq[j] = fma(b, kq[j], cq[j]); cp[j] = fma(b, kp[j], cp[j]); }
-        }
+        HAMK_RK4_STAGES(S, 0, aq, ap, dt, h2, h6, h3, kq, kp, cq, cp, kq, kp, kq, kp, st, tc)   // not dense: the four placeholders
 #pragma unroll
         for (int j = 0; j < N; ++j) {                         // the advanced one goes to wait, the other one is next
           aq[j] = bq[j]; ap[j] = bp[j];

@@ -9,12 +9,8 @@
 //         kept as a double.  Upward: c(y1) > c(y0), target = level + c(y1) period; downward: c(y1) < c(y0), target = level +
 //         c(y0) period.  direction +1 / -1 / 0 counts upward / downward / both; at most ONE crossing per step (dt is expected
 //         to resolve the motion).  A step with a non-finite yc at either end records nothing.
-//     3.  on a crossing: theta in [0, 1] with Yc(theta) = target on RK4's own third-order continuous extension
-//             Y(theta) = y0 + dt [b1 k1 + b2 (k2 + k3) + b4 k4],   b1 = theta - 3 theta^2 / 2 + 2 theta^3 / 3,
-//                                                                  b2 = theta^2 - 2 theta^3 / 3,  b4 = -theta^2 / 2 + 2 theta^3 / 3
-//         (no extra right-hand side, no state carried between steps; Y(1) is the RK4 step) from the secant value
-//         (target - y0c) / (y1c - y0c) by a FIXED number of Newton iterations (kNewton = 4), theta clamped to [0, 1] after each, a
-//         non-finite update leaving theta as it was: known cost, no lane can spin.  The hit is Y(theta) in all 2n components --
+//     3.  on a crossing: theta in [0, 1] with Yc(theta) = target on RK4's own third-order continuous extension Y(theta), by
+//         hamk_fused_rk4.hpp's dense_root (that header states Y and the iteration).  The hit is Y(theta) in all 2n components --
 //         the section component as computed, not snapped to the target -- and goes to row nhit of qhit / phit [max_hits][n][B]
 //         and thit [max_hits][B] IF that row exists; nhit counts it either way, so nhit > max_hits is how a caller learns of an
 //         overflow.  thit = (double)(step0 + step index) + theta, in units of dt.
@@ -23,10 +19,9 @@
 // step0 = N1 and the buffers carried over, bit for bit.  The state's arithmetic does not involve the surface: q, p do not depend
 // on coord, level, period, direction or max_hits.
 //
-// The right-hand side is ham_eqs<S, S::MODE_H> with its default TRIG_FULL, as in hamk_lyap.hpp: no LDS table.  The step loop and
-// the stage loop stay rolled: one copy of the right-hand side.  k1 and k2 + k3 are kept by scalar selects on the wave-uniform stage
-// index and the section component is picked by scalar selects on the wave-uniform coord: no register array is indexed at run time.
-// The crossing branch is lane-divergent and holds arithmetic and stores only.
+// The step is hamk_fused_rk4.hpp's HAMK_RK4_STAGES in its dense form and the section component is picked by its dense_component;
+// the step loop stays rolled as the stage loop does: one copy of the right-hand side.  The crossing branch is lane-divergent and
+// holds arithmetic and stores only.
 //
 // The hit store is the one place that writes beyond what a lane owns by its index alone: the row comes from nhit, memory of the
 // caller's, so it is stored only where (unsigned)row < (unsigned)max_hits, and its index ((i64)row N + j) B + i is 64-bit.
@@ -36,11 +31,9 @@
 // This header rides beside hamk_device.hpp in a COMPANION module of the lane variant (hamk_build.cpp build_companion): the
 // variant's generated source with its HAMK_INSTANTIATE(HamkSys) replaced by HAMK_INSTANTIATE_PSEC(HamkSys).
 #pragma once
-#include "hamk_device.hpp"
+#include "hamk_fused_rk4.hpp"
 
 namespace hamk {
-
-constexpr int kPsecNewton = 4;
 
 // the cell index of a FINITE section component, a double
 HAMK_DEV double psec_cell(double yc, double level, double period) {
@@ -64,56 +57,20 @@ HAMK_DEV void psec_body(double* __restrict__ q, double* __restrict__ p, i64 B, d
 #pragma unroll 1
   for (int s = 0; s < nsteps; ++s) {
     double kq[N], kp[N], cq[N], cp[N], k1q[N], k1p[N], k23q[N], k23p[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) { kq[j] = 0.0; kp[j] = 0.0; cq[j] = aq[j]; cp[j] = ap[j]; k1q[j] = 0.0; k1p[j] = 0.0; k23q[j] = 0.0; k23p[j] = 0.0; }
-#pragma unroll 1
-    for (int sg = 0; sg < 4; ++sg) {
-      const double a = (sg == 0) ? 0.0 : ((sg == 3) ? dt : h2);   // wave-uniform: scalar selects
-      const double b = (sg == 0 || sg == 3) ? h6 : h3;
-      double yq[N], yp[N];
-#pragma unroll
-      for (int j = 0; j < N; ++j) { yq[j] = fma(a, kq[j], aq[j]); yp[j] = fma(a, kp[j], ap[j]); }
-      ham_eqs<S, S::MODE_H>(yq, yp, kq, kp, st, tc);
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        cq[j] = fma(b, kq[j], cq[j]); cp[j] = fma(b, kp[j], cp[j]);
-        k1q[j] = (sg == 0) ? kq[j] : k1q[j]; k1p[j] = (sg == 0) ? kp[j] : k1p[j];                    // k1
-        const double sq = k23q[j] + kq[j], sp = k23p[j] + kp[j];
-        k23q[j] = (sg == 1) ? kq[j] : ((sg == 2) ? sq : k23q[j]);                                    // k2, then k2 + k3
-        k23p[j] = (sg == 1) ? kp[j] : ((sg == 2) ? sp : k23p[j]);
-      }
-    }
+    HAMK_RK4_STAGES(S, 1, aq, ap, dt, h2, h6, h3, kq, kp, cq, cp, k1q, k1p, k23q, k23p, st, tc)
     // the section component before and after, and its three slopes (k4 is in k): coord is wave-uniform
-    double y0c = 0.0, y1c = 0.0, k1c = 0.0, k23c = 0.0, k4c = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const bool isq = coord == j, isp = coord == j + N;
-      y0c = isq ? aq[j] : (isp ? ap[j] : y0c);
-      y1c = isq ? cq[j] : (isp ? cp[j] : y1c);
-      k1c = isq ? k1q[j] : (isp ? k1p[j] : k1c);
-      k23c = isq ? k23q[j] : (isp ? k23p[j] : k23c);
-      k4c = isq ? kq[j] : (isp ? kp[j] : k4c);
-    }
+    double y0c, y1c, k1c, k23c, k4c;
+    dense_component<N>(coord, aq, ap, cq, cp, k1q, k1p, k23q, k23p, kq, kp, y0c, y1c, k1c, k23c, k4c);
     if (!is_nonfinite_bits(y0c) && !is_nonfinite_bits(y1c)) {
       const double c0 = psec_cell(y0c, level, period), c1 = psec_cell(y1c, level, period);
       const bool up = c1 > c0 && direction >= 0, down = c1 < c0 && direction <= 0;
       if (up || down) {                                        // lane-divergent: arithmetic and stores only
         const double target = fma(up ? c1 : c0, period, level);
-        double th = ::fmin(1.0, ::fmax(0.0, (target - y0c) / (y1c - y0c)));      // the secant value, in [0, 1] but for rounding
-#pragma unroll
-        for (int it = 0; it < kPsecNewton; ++it) {
-          const double t2 = th * th, t3 = t2 * th;
-          const double b1 = th - 1.5 * t2 + (2.0 / 3.0) * t3, b2 = t2 - (2.0 / 3.0) * t3, b4 = (2.0 / 3.0) * t3 - 0.5 * t2;
-          const double d1 = 1.0 - 3.0 * th + 2.0 * t2, d2 = 2.0 * th - 2.0 * t2, d4 = 2.0 * t2 - th;
-          const double g = (y0c - target) + dt * (b1 * k1c + b2 * k23c + b4 * k4c);
-          const double dg = dt * (d1 * k1c + d2 * k23c + d4 * k4c);
-          const double tn = th - g / dg;
-          th = is_nonfinite_bits(tn) ? th : ::fmin(1.0, ::fmax(0.0, tn));
-        }
+        const double th = dense_root(y0c, y1c, k1c, k23c, k4c, target, dt);
         const int row = cnt;
         cnt = (int)((unsigned)cnt + 1u);
         if ((unsigned)row < (unsigned)max_hits) {
-          const double t2 = th * th, t3 = t2 * th;
+          const double t2 = th * th, t3 = t2 * th;                 // dense_weights(th), in place: hamk_fused_rk4.hpp says why
           const double b1 = th - 1.5 * t2 + (2.0 / 3.0) * t3, b2 = t2 - (2.0 / 3.0) * t3, b4 = (2.0 / 3.0) * t3 - 0.5 * t2;
 #pragma unroll
           for (int j = 0; j < N; ++j) {
