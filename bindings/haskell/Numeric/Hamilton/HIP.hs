@@ -55,6 +55,8 @@ module Numeric.Hamilton.HIP
   , exitAlive
   , exitNonfinite
   , exitStepsBatch
+  , Recording(..)
+  , recordStepsBatch
   , evolveHamEnsemble
     -- * ensembles resident in HBM, several GPUs from one process
   , DeviceEnsemble
@@ -226,6 +228,9 @@ foreign import ccall safe "hamk_poincare_steps"
 foreign import ccall safe "hamk_exit_steps"
   c_exit_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Ptr Gate -> Int32 -> Ptr Int32 -> Ptr Double
                -> Ptr Double -> Ptr Double -> Int64 -> Ptr Int32 -> Int32 -> IO CInt
+foreign import ccall safe "hamk_record_steps"
+  c_record_steps :: Ptr HamkSystem -> Int64 -> Ptr Double -> Ptr Double -> Double -> Int32 -> Int32 -> Int32 -> Ptr Double -> Ptr Double
+                 -> Ptr Double -> Int64 -> Ptr Int32 -> Int32 -> IO CInt
 foreign import ccall safe "hamk_checkpoint_write"
   c_ck_write :: CString -> Int32 -> Int64 -> Ptr Double -> Ptr Double -> Int32 -> Int64 -> Word64 -> Double -> IO CInt
 foreign import ccall safe "hamk_checkpoint_info"
@@ -619,6 +624,38 @@ exitStepsBatch dt k gates start step0 (HipSystem h) e = withForeignPtr h $ \s ->
       "exitSteps"
   exits <- Exits <$> VS.unsafeFreeze xc <*> VS.unsafeFreeze xt <*> VS.unsafeFreeze xq <*> VS.unsafeFreeze xp
   pure (e', exits)
+
+-- | What 'recordStepsBatch' recorded: the states on the grid of steps (@[recMax][n][B]@ each, row 0 the initial ensemble), their
+--   Hamiltonians (@[recMax][B]@) and how many rows of the run are filled so far; rows at or beyond 'recRows' hold nothing.
+data Recording = Recording
+  { recMax :: !Int
+  , recPositions :: !(VS.Vector Double)
+  , recMomenta :: !(VS.Vector Double)
+  , recEnergy :: !(VS.Vector Double)
+  , recRows :: !Int
+  }
+
+-- | Trajectory recording fused with RK4 ('evolveHam''s rows, Hamilton.hs:433-462, on a fixed step): @k@ RK4 steps of @dt@, and after
+--   every @every@-th step of the run the state and its Hamiltonian written to row buffers inside the launch; row 0 is the initial
+--   ensemble.  @Left maxRows@ starts from zeroed buffers; @Right rec@ with @step0@ = the steps taken so far continues a run bit for
+--   bit.  Rows beyond the buffers are dropped.  One trajectory per lane: @n <= 16@.
+recordStepsBatch :: forall m n. KnownNat n => Double -> Int -> Int -> Either Int Recording -> Int64 -> HipSystem m n -> Ensemble n
+                 -> IO (Ensemble n, Recording)
+recordStepsBatch dt k every start step0 (HipSystem h) e = withForeignPtr h $ \s -> do
+  let rows = either id recMax start
+      nb = ensSize e
+      nq = VS.length (ensPositions e)
+      begin f z = either (const (pure z)) (pure . f) start
+      upto = (fromIntegral step0 + k) `div` every + 1
+      filled = if k > 0 && nb > 0 then min rows upto else either (const 0) recRows start
+  rq <- VS.thaw =<< begin recPositions (VS.replicate (rows * nq) 0)
+  rp <- VS.thaw =<< begin recMomenta (VS.replicate (rows * nq) 0)
+  rh <- VS.thaw =<< begin recEnergy (VS.replicate (rows * nb) 0)
+  e' <- VSM.unsafeWith rq $ \prq -> VSM.unsafeWith rp $ \prp -> VSM.unsafeWith rh $ \prh ->
+    inPlace e (\b pq pp -> c_record_steps s b pq pp dt (fromIntegral k) (fromIntegral every) (fromIntegral rows) prq prp prh step0 nullPtr memHost)
+      "recordSteps"
+  out <- Recording rows <$> VS.unsafeFreeze rq <*> VS.unsafeFreeze rp <*> VS.unsafeFreeze rh <*> pure filled
+  pure (e', out)
 
 -- | 'evolveHam' (Hamilton.hs:433-462) for every member: one ensemble per requested time,
 --   element 0 being the initial ensemble.

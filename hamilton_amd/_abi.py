@@ -115,6 +115,9 @@ SIGNATURES = {
     "hamk_exit_steps": (ctypes.c_int, [_h, _i64, _dp, _dp, _f64, _i32, ctypes.c_void_p, _i32, _ip, _dp, _dp, _dp, _i64, _ip, _i32]),
     "hamk_exit_source": (ctypes.c_char_p, [_h]),
     "hamk_exit_build_info": (ctypes.c_char_p, [_h]),
+    "hamk_record_steps": (ctypes.c_int, [_h, _i64, _dp, _dp, _f64, _i32, _i32, _i32, _dp, _dp, _dp, _i64, _ip, _i32]),
+    "hamk_record_source": (ctypes.c_char_p, [_h]),
+    "hamk_record_build_info": (ctypes.c_char_p, [_h]),
     "hamk_system_set_gsl_api": (ctypes.c_int, [_h, _i32]),
     "hamk_system_get_gsl_api": (_i32, [_h]),
     "hamk_system_code_object": (_i64, [_h, _i32, ctypes.c_void_p, _i64]),

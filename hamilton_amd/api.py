@@ -241,7 +241,7 @@ class System:
         text = fn(self._h)
         if text is None:
             msg = _abi.lib().hamk_last_error().decode("utf-8", "replace")
-            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper", "the Poincare-section stepper", "the exit-time stepper")) or "unsupported" in msg
+            unsupported = msg.startswith(("the symplectic stepper", "the Lyapunov stepper", "the Poincare-section stepper", "the exit-time stepper", "the recording stepper")) or "unsupported" in msg
             raise HamkError(_abi.HAMK_ERR_UNSUPPORTED if unsupported else _abi.HAMK_ERR_COMPILE, msg)
         return text.decode()
 
@@ -284,6 +284,16 @@ class System:
     def exit_build_info(self) -> str:
         """One `build_info`-format line for hamk_exit_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
         return self._symplectic_text(_abi.lib().hamk_exit_build_info)
+
+    @property
+    def record_source(self) -> str:
+        """Source of the recording stepper's companion module (hamk_record_source; builds it if needed, needs no GPU)."""
+        return self._symplectic_text(_abi.lib().hamk_record_source)
+
+    @property
+    def record_build_info(self) -> str:
+        """One `build_info`-format line for hamk_rec_steps_k: bytes, spilled SGPRs / VGPRs, allocated VGPRs, function symbols."""
+        return self._symplectic_text(_abi.lib().hamk_record_build_info)
 
     def kernel_bytes(self, kernel: str) -> int:
         return int(_abi.lib().hamk_system_kernel_bytes(self._h, kernel.encode()))
@@ -796,6 +806,89 @@ def exitSteps(dt: float, nsteps: int, s: System, ph: Phase, gates, exits: Option
     s._after(st, qa.single, "exitSteps")
     drop = (lambda x: x[..., 0]) if qa.single else (lambda x: x)
     return Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Exits(drop(code), drop(te), drop(eq), drop(ep))
+
+
+class Record:
+    """What recordSteps recorded: `positions`, `momenta` [max_rows, n, B] or None (row k: the state after k * every steps, row 0
+    the initial state), `energy` [max_rows, B] or None (the Hamiltonian of that state) and `rows`: how many rows of the run are
+    filled so far -- rows at or beyond it hold nothing.  For one trajectory the B axis is dropped."""
+
+    def __init__(self, positions, momenta, energy, rows):
+        self.positions = positions
+        self.momenta = momenta
+        self.energy = energy
+        self.rows = rows
+
+    def __repr__(self):
+        have = self.positions if self.positions is not None else self.energy
+        return f"Record {{rows = {self.rows}, max_rows = {have.shape[0]}}}"
+
+
+def recordSteps(dt: float, nsteps: int, every: int, s: System, ph: Phase, max_rows: Optional[int] = None, states: bool = True,
+                energy: bool = False, record: Optional[Record] = None, step0: int = 0, inplace: bool = False):
+    """Trajectory recording fused with RK4 (hamk_record_steps; evolveHam's rows on a fixed step): `nsteps` RK4 steps of `dt`, and
+    the state (states=True) and / or its Hamiltonian (energy=True) after every `every`-th step of the run written to row buffers
+    inside the launch; row 0 is the initial state.  Returns (Phase, Record).  record=None: a new run with buffers of `max_rows` rows
+    (None: exactly the rows the run fills, (step0 + nsteps) // every + 1); rows beyond max_rows are dropped.  Passing the returned
+    Record back with step0 = the steps taken so far continues the run bit for bit (its buffers then say what is recorded and how
+    many rows there are).  inplace=True advances the given arrays (state, and the Record's buffers where given) without copying.
+    One trajectory per lane: n <= 16."""
+    qa, pa = _pair(ph.positions, "positions", ph.momenta, "momenta", s.n)
+    if inplace:
+        _in_place(qa, ph.positions, "positions"); _in_place(pa, ph.momenta, "momenta")
+    q, p = (qa.a, pa.a) if inplace else (qa.clone(), pa.clone())
+    if int(every) < 1:
+        raise ValueError("every must be at least 1")
+    if record is None:
+        rows = (int(step0) + int(nsteps)) // int(every) + 1 if max_rows is None else int(max_rows)
+        if rows < 1:
+            raise ValueError("max_rows must be at least 1")
+        if not states and not energy:
+            raise ValueError("nothing to record: states and energy are both off")
+        rq = qa.like(s.n, lead=(rows,), zero=True) if states else None
+        rp = qa.like(s.n, lead=(rows,), zero=True) if states else None
+        rh = qa.like(None, lead=(rows,), zero=True) if energy else None
+        before = 0
+    else:
+        have = record.positions if record.positions is not None else record.energy
+        if have is None or (record.positions is None) != (record.momenta is None):
+            raise ValueError("record: positions and momenta go together, and at least one of them and energy must be there")
+        rows = int(have.shape[0])
+        bufs = []
+        for a, shape, name in ((record.positions, (rows, s.n, qa.B), "record.positions"), (record.momenta, (rows, s.n, qa.B), "record.momenta"),
+                               (record.energy, (rows, qa.B), "record.energy")):
+            if a is None:
+                bufs.append(None)
+                continue
+            if _is_torch(a) != qa.device or (qa.device and a.device != qa.a.device):
+                raise ValueError(f"{name} must live in the memory of the state")
+            if not qa.device:
+                a = np.asarray(a)
+            if a.dtype != (torch.float64 if qa.device else np.float64) or int(np.prod(a.shape)) != int(np.prod(shape)):
+                raise ValueError(f"{name}: expected float64 of shape {shape}")
+            b = a.reshape(shape)
+            if qa.device:
+                b = b.contiguous()
+                same = b.data_ptr() == a.data_ptr()
+                b = b if inplace else b.clone()
+            else:
+                b = np.ascontiguousarray(b)
+                same = b.ctypes.data == a.ctypes.data
+                b = b if inplace else b.copy()
+            if inplace and not same:
+                raise ValueError(f"inplace=True needs {name} contiguous")
+            bufs.append(b)
+        rq, rp, rh = bufs
+        before = int(record.rows)
+    # zeroed: with nothing to do (nsteps = 0, an empty ensemble) the call returns HAMK_OK without writing status or any row
+    st = qa.like(None, "i4", zero=True)
+    with s._on(qa):
+        _abi.check(_abi.lib().hamk_record_steps(s._h, qa.B, _ptr(q), _ptr(p), float(dt), int(nsteps), int(every), rows, _ptr(rq), _ptr(rp), _ptr(rh),
+                                                int(step0), _ptr(st), qa.mem))
+    s._after(st, qa.single, "recordSteps")
+    filled = min(rows, (int(step0) + int(nsteps)) // int(every) + 1) if (int(nsteps) > 0 and qa.B > 0) else before
+    drop = (lambda x: None if x is None else x[..., 0]) if qa.single else (lambda x: x)
+    return Phase(_shape_out(q, qa.single), _shape_out(p, qa.single)), Record(drop(rq), drop(rp), drop(rh), filled)
 
 
 # ---------------------------------------------------------------------------------------

@@ -708,7 +708,7 @@ int hamk_rk4_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, i
 }
 
 // ---- the lane variant's companion modules: symplectic stepping (hamk_symp.hpp), Lyapunov stepping (hamk_lyap.hpp), ------
-// ---- Poincare sections (hamk_psec.hpp), first-exit times (hamk_exit.hpp)
+// ---- Poincare sections (hamk_psec.hpp), first-exit times (hamk_exit.hpp), trajectory recording (hamk_rec.hpp)
 // The lane variant of a handle that can run a companion's stepper, that companion module built: n <= 16 and no other mapping
 // stated.  AUTO never leaves the lane mapping here, whatever B is (its small-ensemble rule for 11 <= n <= 16 was measured on RK4).
 static int companion_variant(hamk_system* s, CompanionKind kind, Variant** out) {
@@ -749,6 +749,8 @@ const char* hamk_poincare_source(hamk_system* s) { return companion_text(s, COMP
 const char* hamk_poincare_build_info(hamk_system* s) { return companion_text(s, COMPANION_PSEC, true); }
 const char* hamk_exit_source(hamk_system* s) { return companion_text(s, COMPANION_EXIT, false); }
 const char* hamk_exit_build_info(hamk_system* s) { return companion_text(s, COMPANION_EXIT, true); }
+const char* hamk_record_source(hamk_system* s) { return companion_text(s, COMPANION_REC, false); }
+const char* hamk_record_build_info(hamk_system* s) { return companion_text(s, COMPANION_REC, true); }
 
 int hamk_symplectic_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t order,
                           int32_t iters, double* residual, int32_t* status, int32_t mem) {
@@ -883,6 +885,54 @@ int hamk_exit_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, 
   }
   TRY(st.out(status, (size_t)B, &dst));
   TRY(launch_exit(s, B, xq, xp, c, dst));
+  return st.finish();
+}
+
+int hamk_record_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t every, int32_t max_rows,
+                      double* qout, double* pout, double* hout, int64_t step0, int32_t* status, int32_t mem) {
+  TRY(check_call(s, B, mem));
+  if (!q || !p) return fail(HAMK_ERR_INVALID, "null q / p");
+  if ((qout == nullptr) != (pout == nullptr)) return fail(HAMK_ERR_INVALID, "qout and pout: both null or both given");
+  if (!qout && !hout) return fail(HAMK_ERR_INVALID, "nothing to record: qout / pout and hout are all null");
+  if (nsteps < 0) return fail(HAMK_ERR_INVALID, "negative nsteps");
+  if (every < 1) return fail(HAMK_ERR_INVALID, "every must be at least 1 (RK4 steps per recorded row)");
+  if (max_rows < 1) return fail(HAMK_ERR_INVALID, "max_rows must be at least 1");
+  const int64_t n = s->base.n;
+  // the row buffers hold max_rows n B doubles each: at most 2^48 of them, so that their byte count and the kernel's 64-bit index stay
+  // far inside an int64 (max_rows n <= 2^31 * 16 cannot overflow before the division)
+  if (B > 0 && (int64_t)max_rows * n > (INT64_C(1) << 48) / B) return fail(HAMK_ERR_INVALID, "max_rows * n * B exceeds 2^48 elements");
+  if (step0 < 0) return fail(HAMK_ERR_INVALID, "negative step0");
+  if (step0 > (INT64_C(1) << 52)) return fail(HAMK_ERR_INVALID, "step0 exceeds 2^52");
+  if (!std::isfinite(dt)) return fail(HAMK_ERR_INVALID, "dt is not finite");
+  Variant* v = nullptr;
+  TRY(companion_variant(s, COMPANION_REC, &v));
+  if (B == 0 || nsteps == 0) return HAMK_OK;
+  TRY(companion_load(s, v, COMPANION_REC));
+  Stager st(s, mem);
+  const size_t cnt = (size_t)n * B;
+  double *xq, *xp; int32_t* dst;
+  RecCall c{dt, nsteps, every, max_rows, qout, pout, hout, step0, 0};
+  TRY(st.inout(q, cnt, &xq));
+  TRY(st.inout(p, cnt, &xp));
+  if (mem == HAMK_MEM_HOST) {
+    // The rows this call fills are known here: first .. last, row 0 only for a run's first call.  Exactly those are staged, as
+    // outputs (the kernel never reads a row) with row_base = first, and copied back: every other row of the caller's buffers keeps
+    // its bits without a copy in.
+    const int64_t first = step0 == 0 ? 0 : step0 / every + 1;
+    const int64_t last = std::min<int64_t>((int64_t)max_rows - 1, (step0 + nsteps) / every);
+    c.qout = c.pout = c.hout = nullptr;                      // no row of this call fits: the kernel steps, and stores q, p alone
+    if (last >= first) {
+      const size_t rows = (size_t)(last - first + 1);
+      c.row_base = first;
+      if (qout) {
+        TRY(st.out(qout + (size_t)first * cnt, rows * cnt, &c.qout));
+        TRY(st.out(pout + (size_t)first * cnt, rows * cnt, &c.pout));
+      }
+      if (hout) TRY(st.out(hout + (size_t)first * B, rows * (size_t)B, &c.hout));
+    }
+  }
+  TRY(st.out(status, (size_t)B, &dst));
+  TRY(launch_rec(s, B, xq, xp, c, dst));
   return st.finish();
 }
 

@@ -49,6 +49,9 @@ static const char kPsecHeader[] =
 static const char kExitHeader[] =
 #include "hamk_exit_src.inc"
     ;
+static const char kRecHeader[] =
+#include "hamk_rec_src.inc"
+    ;
 static const char kFusedRk4Header[] =
 #include "hamk_fused_rk4_src.inc"
     ;
@@ -70,6 +73,7 @@ const CompanionDesc kCompanions[COMPANION__COUNT] = {
     {"hamk_lyap.hpp", kLyapHeader, sizeof kLyapHeader, true, "HAMK_INSTANTIATE_LYAP", "hamk_lyap_steps_k", "the Lyapunov stepper"},
     {"hamk_psec.hpp", kPsecHeader, sizeof kPsecHeader, true, "HAMK_INSTANTIATE_PSEC", "hamk_psec_steps_k", "the Poincare-section stepper"},
     {"hamk_exit.hpp", kExitHeader, sizeof kExitHeader, true, "HAMK_INSTANTIATE_EXIT", "hamk_exit_steps_k", "the exit-time stepper"},
+    {"hamk_rec.hpp", kRecHeader, sizeof kRecHeader, true, "HAMK_INSTANTIATE_REC", "hamk_rec_steps_k", "the recording stepper"},
 };
 }  // namespace
 const char* companion_kernel_name(CompanionKind kind) { return kCompanions[kind].kernel; }
@@ -382,7 +386,7 @@ size_t chosen_kernel_bytes(const Variant* s, int k) {
   return kernel_code_bytes(s->use2[k] ? s->code2 : s->code, kKernelNames[k]);
 }
 
-// ---- the lane variant's companion modules (hamk_symp.hpp, hamk_lyap.hpp, hamk_psec.hpp, hamk_exit.hpp) ---------------------------
+// ---- the lane variant's companion modules (hamk_symp.hpp, hamk_lyap.hpp, hamk_psec.hpp, hamk_exit.hpp, hamk_rec.hpp) ---------------
 // A per-system module holds exactly the nine kernels of HAMK_INSTANTIATE (tests/test_abi.py counts its function symbols and
 // the rows of build_info), and its cache key covers the whole text of hamk_device.hpp: a tenth kernel there would move every
 // existing module.  So hamk_symp_steps_k, hamk_lyap_steps_k, hamk_psec_steps_k and hamk_exit_steps_k each live in a module of their own: the lane variant's generated

@@ -363,6 +363,10 @@ int launch_exit(hamk_system* s, int64_t B, double* q, double* p, const ExitCall&
   return launch_kernel<sig_exit::hamk_exit_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].companion_fn[COMPANION_EXIT], s->cur->stream, B, 256, q, p, B, c.dt, c.nsteps, c.gates,
                                                         c.code, c.texit, c.qexit, c.pexit, c.step0, status);
 }
+int launch_rec(hamk_system* s, int64_t B, double* q, double* p, const RecCall& c, int* status) {
+  return launch_kernel<sig_rec::hamk_rec_steps_k>::on(s->cur->mod[HAMK_MAP_LANE].companion_fn[COMPANION_REC], s->cur->stream, B, 256, q, p, B, c.dt, c.nsteps, c.every,
+                                                      c.max_rows, c.qout, c.pout, c.hout, c.step0, c.row_base, status);
+}
 int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx) {
   return launch_kernel<sig::hamk_sample_k>::on(d->sample_fn, d->stream, B, 256, q, qd, B, first_index, seed, n, bx);
 }

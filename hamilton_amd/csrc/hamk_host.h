@@ -3,7 +3,7 @@
 //   hamk_dispatch.cpp  options -> specialisations (which lanes serve a trajectory, bodies, sincos policy ...), device
 //                      binding, the typed launchers (launch_*), the first-use self-check
 //   hamk_api.cpp       the C ABI of include/hamk.h: argument checks, host-pointer staging, checkpoints
-// and the ONE host-side statement of every kernel's parameter list (namespace sig below, sig_lyap, sig_psec and sig_exit beside it): launch_kernel<Sig> builds the argument
+// and the ONE host-side statement of every kernel's parameter list (namespace sig below, sig_lyap, sig_psec, sig_exit and sig_rec beside it): launch_kernel<Sig> builds the argument
 // array from it and is the only caller of hipModuleLaunchKernel; tests/test_kernel_signatures.py holds the table against the
 // device headers.
 #pragma once
@@ -39,7 +39,7 @@ enum KernelId { K_RK4, K_HAMEQS, K_COORDS, K_TO_PHASE, K_FROM_PHASE, K_OBSERVE, 
 extern const char* const kKernelNames[K__COUNT];
 
 // The lane variant's companion modules: one extra kernel each, in a module of its own (hamk_build.cpp build_companion).
-enum CompanionKind { COMPANION_NONE = -1, COMPANION_SYMP = 0, COMPANION_LYAP = 1, COMPANION_PSEC = 2, COMPANION_EXIT = 3, COMPANION__COUNT = 4 };
+enum CompanionKind { COMPANION_NONE = -1, COMPANION_SYMP = 0, COMPANION_LYAP = 1, COMPANION_PSEC = 2, COMPANION_EXIT = 3, COMPANION_REC = 4, COMPANION__COUNT = 5 };
 
 struct Sha256 {
   uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
@@ -111,7 +111,7 @@ struct Variant {
   int self_check_rebuilds = 0;
   bool forced_rk4_body = false, forced_rkf_body = false;
   // the lane variant's COMPANION modules, one per kind (hamk_symp.hpp: hamk_symp_steps_k; hamk_lyap.hpp: hamk_lyap_steps_k;
-  // hamk_psec.hpp: hamk_psec_steps_k; hamk_exit.hpp: hamk_exit_steps_k), each
+  // hamk_psec.hpp: hamk_psec_steps_k; hamk_exit.hpp: hamk_exit_steps_k; hamk_rec.hpp: hamk_rec_steps_k), each
   // built the first time its entry points ask for it; its own source, code object and one-line description -- no part of `source`,
   // `code`, `build_info` or the kernel counts above
   struct Companion {
@@ -245,6 +245,10 @@ static_assert(sizeof(HamkGates) == 8 * sizeof(double) + 6 * sizeof(int), "HamkGa
 namespace sig_exit {
 using hamk_exit_steps_k = void(double*, double*, long long, double, int, HamkGates, int*, double*, double*, double*, long long, int*);
 }  // namespace sig_exit
+// hamk_rec.hpp's kernel, the recording companion module's (tests/test_record.py holds it against the device header)
+namespace sig_rec {
+using hamk_rec_steps_k = void(double*, double*, long long, double, int, int, int, double*, double*, double*, long long, long long, int*);
+}  // namespace sig_rec
 
 // A launch over B trajectories, per_block of them to a block of 256 threads.  The arguments arrive BY VALUE as the signature's own
 // parameter types -- the compiler converts or refuses -- and the argument array is built from them here, nowhere else.
@@ -314,7 +318,7 @@ int launch_observe(hamk_system* s, int64_t B, const double* q, const double* p, 
 int launch_observe_config(hamk_system* s, int64_t B, const double* q, const double* qd, double* ke, double* lag);
 int launch_rkf45(hamk_system* s, int64_t B, const RkfCall& c);
 int launch_scribble(hamk_system* s, unsigned seed);         // 2048 blocks, whatever the mapping
-// ... the companion modules' steppers (loaded by hamk_symplectic_steps / hamk_lyapunov_steps / hamk_poincare_steps / hamk_exit_steps) and the sampler (loaded by
+// ... the companion modules' steppers (loaded by hamk_symplectic_steps / hamk_lyapunov_steps / hamk_poincare_steps / hamk_exit_steps / hamk_record_steps) and the sampler (loaded by
 // hamk_sample_batch): one lane each
 int launch_lyap(hamk_system* s, int64_t B, double* q, double* p, double* wq, double* wp, double dt, int nintervals, int every, double d0, double* logsum, int* status);
 struct PsecCall {             // hamk_psec_steps_k's arguments after (q, p, B), as hamk_poincare_steps checked them
@@ -327,6 +331,11 @@ struct ExitCall {             // hamk_exit_steps_k's arguments after (q, p, B), 
   int* code; double *texit, *qexit, *pexit; long long step0;
 };
 int launch_exit(hamk_system* s, int64_t B, double* q, double* p, const ExitCall& c, int* status);
+struct RecCall {              // hamk_rec_steps_k's arguments after (q, p, B), as hamk_record_steps checked them
+  double dt; int nsteps, every, max_rows;
+  double *qout, *pout, *hout; long long step0, row_base;
+};
+int launch_rec(hamk_system* s, int64_t B, double* q, double* p, const RecCall& c, int* status);
 int launch_symp(hamk_system* s, int64_t B, double* q, double* p, int nsteps, int nsub, double ha, double hb, int iters, double* residual, int* status);
 int launch_sample(DevState* d, int64_t B, double* q, double* qd, long long first_index, unsigned long long seed, int n, const HamkBoxes& bx);
 

@@ -528,6 +528,39 @@ inline Phase exitSteps(double dt, int nsteps, System& s, const Phase& ph, const 
                         exits.t.data(), exits.positions.data(), exits.momenta.data(), step0, s.last_status.data(), HAMK_MEM_HOST));
   return out;
 }
+// Trajectory recording fused with RK4 (hamk_record_steps; evolveHam's rows, :433-462, on a fixed step): `nsteps` RK4 steps of dt,
+// and after every `every`-th step of the run the state and / or its Hamiltonian written to row buffers inside the launch; row 0 is
+// the initial state; n <= 16.  positions / momenta: [max_rows][n][B] (with_states), energy: [max_rows][B] (with_energy); rows: how
+// many rows of the run are filled so far -- rows at or beyond it hold nothing, rows beyond max_rows are dropped.  An EMPTY Record is
+// sized to max_rows zeroed rows first; feeding the same Record to the next call with step0 = the steps taken so far continues the
+// run bit for bit.
+struct Record {
+  int max_rows = 16;
+  bool with_states = true, with_energy = false;
+  std::vector<double> positions, momenta, energy;
+  int64_t rows = 0;
+};
+inline Phase recordSteps(double dt, int nsteps, int every, System& s, const Phase& ph, Record& rec, int64_t step0 = 0) {
+  Phase out = ph;
+  const size_t rows = (size_t)(rec.max_rows > 0 ? rec.max_rows : 0), nb = (size_t)ph.B;
+  const size_t nq = rec.with_states ? rows * ph.positions.size() : 0, nh = rec.with_energy ? rows * nb : 0;
+  if (rec.positions.empty() && rec.momenta.empty() && rec.energy.empty()) {
+    rec.positions.assign(nq, 0.0);
+    rec.momenta.assign(nq, 0.0);
+    rec.energy.assign(nh, 0.0);
+  }
+  if (rec.positions.size() != nq || rec.momenta.size() != nq || rec.energy.size() != nh)
+    throw std::invalid_argument("recordSteps: rec must hold max_rows rows of the ensemble of the state");
+  s.last_status.assign(nb, 0);
+  check(hamk_record_steps(s.handle(), ph.B, out.positions.data(), out.momenta.data(), dt, nsteps, every, rec.max_rows,
+                          rec.with_states ? rec.positions.data() : nullptr, rec.with_states ? rec.momenta.data() : nullptr,
+                          rec.with_energy ? rec.energy.data() : nullptr, step0, s.last_status.data(), HAMK_MEM_HOST));
+  if (nsteps > 0 && ph.B > 0) {
+    const int64_t upto = (step0 + nsteps) / every + 1;
+    rec.rows = upto < rec.max_rows ? upto : rec.max_rows;
+  }
+  return out;
+}
 
 // ---------------------------------------------------------------------------------------
 // Ensembles resident in HBM (no reference counterpart: the reference holds one trajectory on the
@@ -622,6 +655,13 @@ inline void exitSteps(double dt, int nsteps, System& s, DevicePhase& d, const st
                       DeviceArray& qexit, DeviceArray& pexit, int64_t step0 = 0) {      // in place, asynchronous
   check(hamk_exit_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, gates.data(), (int32_t)gates.size(),
                         code.as<int32_t>(), texit.as<double>(), qexit.as<double>(), pexit.as<double>(), step0, d.status.as<int32_t>(), HAMK_MEM_DEVICE));
+}
+// qout, pout: max_rows n B doubles (both may be an empty DeviceArray's null), hout: max_rows B doubles (may be one too) -- on the
+// device, the caller's; the rows this call fills are written, no row is read
+inline void recordSteps(double dt, int nsteps, int every, System& s, DevicePhase& d, int max_rows, DeviceArray& qout, DeviceArray& pout,
+                        DeviceArray& hout, int64_t step0 = 0) {      // in place, asynchronous
+  check(hamk_record_steps(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), dt, nsteps, every, max_rows, qout.as<double>(),
+                          pout.as<double>(), hout.as<double>(), step0, d.status.as<int32_t>(), HAMK_MEM_DEVICE));
 }
 inline void stepHam(double r, System& s, DevicePhase& d) {                     // :390-402, in place, asynchronous
   check(hamk_step_ham_batch(s.handle(), d.B, d.positions.as<double>(), d.momenta.as<double>(), r, d.status.as<int32_t>(), nullptr, HAMK_MEM_DEVICE));

@@ -26,6 +26,7 @@
  *   (no counterpart; which trajectories are chaotic)    hamk_lyapunov_steps   (largest Lyapunov exponent, fused with RK4)
  *   (no counterpart; the surface of section)            hamk_poincare_steps   (crossings recorded inside a fused RK4 launch)
  *   (no counterpart; first-exit times)                  hamk_exit_steps       (when and where a trajectory leaves a box; it then stops)
+ *   evolveHam's rows :433-462, on a fixed step          hamk_record_steps     (state / Hamiltonian rows recorded inside a fused RK4 launch)
  *
  * The reference evaluates ONE trajectory per call on the CPU through `ad`
  * (AD), hmatrix (LAPACK/BLAS) and hmatrix-gsl (GSL odeiv).  This library
@@ -477,6 +478,38 @@ int hamk_exit_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, 
  * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
 const char* hamk_exit_source(hamk_system* s);
 const char* hamk_exit_build_info(hamk_system* s);
+
+/* Trajectory recording fused with classic RK4: `nsteps` RK4 steps of dt IN PLACE on q, p (the right-hand side and the step of the
+ * Lyapunov stepper, one trajectory per lane), and on a grid of steps the state and / or its Hamiltonian written to fixed-size row
+ * buffers from inside the launch: evolveHam's rows (Hamilton.hs:433-462, row 0 the initial state) on a fixed step.
+ *   Rows.  G is the number of steps taken in the whole run: step0 (the caller's count of steps already taken) at entry,
+ *   step0 + s + 1 after the call's step s.  Where G is a multiple of `every`, the state after G steps is row k = G / every.  Row 0
+ *   is recorded at entry and only if step0 == 0: the state as given, bit for bit.  A row is recorded after every step whose G in
+ *   (step0, step0 + nsteps] is a multiple of `every`.  A row k >= max_rows is dropped; rows outside this call's range are never
+ *   written, and no row is ever read.  After the call min(max_rows, (step0 + nsteps) / every + 1) rows of the run are filled.
+ *   Outputs.  qout, pout: [max_rows][n][B], both NULL or both given; row k is an [n][B] block in this header's layout, so every
+ *   *_batch entry point applies to it as it stands.  hout: [max_rows][B], may be NULL: the Hamiltonian of the recorded state
+ *   (hamk_observe_batch's h; evaluated only where a row is recorded).  At least one of the two groups must be given; hout alone is
+ *   the energy curve of an ensemble at 1 / (4n) of the memory.
+ *   So: N steps in one call equal N1 + N2 in two calls with step0 = N1 and the buffers carried over, bit for bit on q, p and every
+ *   row; the final q, p do not depend on every, max_rows or on which outputs are given.  The rows are this stepper's bits; they are
+ *   not promised equal to hamk_rk4_steps's.
+ *   status may be NULL.  status: HAMK_ST_SINGULAR from any right-hand side and from the Hamiltonian's solve, HAMK_ST_NONFINITE where
+ *   the final state is not finite; a non-finite trajectory's rows hold what the arithmetic gives.
+ *   HAMK_ERR_INVALID: a null handle, q or p, exactly one of qout / pout, all three outputs NULL, B < 0, nsteps < 0, every < 1,
+ *   max_rows < 1, max_rows n B beyond 2^48, step0 < 0 or beyond 2^52, dt not finite, an unknown mem.  One trajectory per lane:
+ *   n <= 16; HAMK_ERR_UNSUPPORTED for n > 16 or a handle whose options state HAMK_MAP_QUAD / HAMK_MAP_WAVE; mapping = HAMK_AUTO
+ *   ALWAYS runs on the one-trajectory-per-lane module, whatever B is.
+ *   HAMK_MEM_DEVICE: asynchronous on the handle's stream.  HAMK_MEM_HOST: staged; exactly the rows this call fills are copied back,
+ *   every other row of the caller's buffers keeps its bits, and the buffers are not copied in.  B == 0 or nsteps == 0: HAMK_OK,
+ *   nothing launched and nothing written, row 0 included.  The kernel (hamk_rec.hpp) lives in a companion module of the lane
+ *   module, built the first time one of these three entry points asks for it; the first-use self-check does not cover it.     */
+int hamk_record_steps(hamk_system* s, int64_t B, double* q, double* p, double dt, int32_t nsteps, int32_t every, int32_t max_rows,
+                      double* qout, double* pout, double* hout, int64_t step0, int32_t* status, int32_t mem);
+/* Source / one build_info-format line (kernel, bytes, spilled SGPRs and VGPRs, allocated VGPRs, function symbols) of that
+ * companion module; builds it if needed; needs no GPU.  NULL + hamk_last_error() where the stepper is unsupported.     */
+const char* hamk_record_source(hamk_system* s);
+const char* hamk_record_build_info(hamk_system* s);
 
 /* stepHam dt: adaptive RKF45 with GSL's standard controller from 0 to dt,
  * h0 = dt/100, eps_abs = eps_rel = 1.49012e-08, IN PLACE.  Hamilton.hs:390-402,

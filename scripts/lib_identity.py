@@ -5,8 +5,8 @@
     python scripts/lib_identity.py --compare a.json b.json [...]        exit 1 and the differing entries if any two tables differ
 
 Cases: every golden system on the lane mapping, chain12 / chain17 on the quad mapping, the smallest dense-quad member of
-tests/rect_family.py, chain17 on the wave mapping, chain33.  Per case the generated source and build_info; the three existing companion modules' sources
-(symplectic, Lyapunov, Poincare) for the lane systems; both code objects for doublePendulum, chain8, chain12 (quad) and chain17 (wave)."""
+tests/rect_family.py, chain17 on the wave mapping, chain33.  Per case the generated source and build_info; the four existing companion modules' sources
+(symplectic, Lyapunov, Poincare, exit-time) for the lane systems; both code objects for doublePendulum, chain8, chain12 (quad) and chain17 (wave)."""
 import argparse
 import hashlib
 import json
@@ -37,6 +37,7 @@ def one(lib, name, mapping):
         row["symplectic_source"] = sha(s.symplectic_source)
         row["lyapunov_source"] = sha(s.lyapunov_source)
         row["poincare_source"] = sha(s.poincare_source)
+        row["exit_source"] = sha(s.exit_source)
     if (name, mapping) in WITH_CODE:
         row["code_object_0"], row["code_object_1"] = sha(s.code_object(0)), sha(s.code_object(1))
     return row

@@ -100,6 +100,9 @@ def jobs():
     # the exit-time stepper's companion module (hamk_exit.hpp) of the systems tests/test_gpu_exit.py steps, its three anchors included
     for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "anchor_rotor", "anchor_oscillator", "anchor_free"):
         out.append((f"exit_{n}", {}, False))
+    # the recording stepper's companion module (hamk_rec.hpp) of the systems tests/test_gpu_record.py steps, its anchor and twoBody included
+    for n in ("pendulum", "doublePendulum", "opcodeZoo", "chain8", "twoBody", "anchor_oscillator"):
+        out.append((f"rec_{n}", {}, False))
     return rect + out
 
 
@@ -143,6 +146,12 @@ def build(job):
         elif name.startswith("psec_anchor_"):
             import test_poincare
             return name, env, test_poincare.anchor_system(name[12:]).poincare_build_info.strip()
+        elif name.startswith("rec_anchor_"):
+            import test_lyapunov
+            return name, env, test_lyapunov.anchor_system(name[11:]).record_build_info.strip()
+        elif name.startswith("rec_"):
+            s = api.system_from_spec(examples.get(name[4:]))
+            return name, env, s.record_build_info.strip()
         elif name.startswith("exit_anchor_"):
             import test_exit
             return name, env, test_exit.anchor_system(name[12:]).exit_build_info.strip()
